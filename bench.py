@@ -2,7 +2,12 @@
 """Headline benchmark: train iters/sec + forward Mpix/sec, 1M Gaussians @ 1920x1080, SH degree 3
 (BASELINE.json metric; configs[2] at N=1, configs[3] view-sharded at N>1).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+    A plain run sets up, warms up, times the K steps, writes two further steps' results with
+    --dump-outputs, and prints the headline line (metric, value, unit, ms_per_step, ...).  --full
+    adds every other measurement described below (stage profile, densify cost, read-back / bracket /
+    API legs, forward throughput, roofline, CPU baseline); without it their iterations still run,
+    unmeasured, so the timed window starts from the same model state either way.
     (N>1 under a launcher: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
      127.0.0.1 ... bench.py --gpus N ...; WORLD_SIZE must equal --gpus.  N>1 without one: bench.py starts
      that launcher itself as a child process, before anything touches the GPU, and exits with its code)
@@ -12,9 +17,9 @@ lr update, render forward, L1+SSIM loss, backward through the MI355X rasterizer,
 exchange), densification statistics, densify/prune at every multiple of 100, Adam.  Iteration
 numbers (they drive the lr schedule and the densify/prune events, train.py:136-143):
   warmup   W iterations ending on densify iteration 900 (allocator and densify path warm)
-  profile  901 .. 900+PW: every stage event-timed (the per-kernel breakdown)
-  999, 1000  each run alone between device syncs: an ordinary and a densify/prune iteration
-           (densify_iter_ms, densify_extra_ms)
+  profile  901 .. 900+PW: with --full every stage event-timed (the per-kernel breakdown)
+  999, 1000  an ordinary and a densify/prune iteration; with --full each runs alone between device
+           syncs (densify_iter_ms, densify_extra_ms)
   timed    1001 .. 1000+K: it starts right after a densify iteration, so it holds exactly
            floor(K/100) densify/prune events (iterations 1100, 1200, ...) — the reference's
            1-in-100 share, rounded down; `iters_per_s_1in100` adds the measured extra cost of one
@@ -24,7 +29,13 @@ value = iterations all ranks completed in the timed window / wall time (max over
 Data: synthetic and seeded (no datasets offline) — 1M random Gaussians (SURVEY §8(d) bench
 variant), 200 Fibonacci-sphere cameras, ground-truth images rendered from a second random model.
 
-Extra objects on the JSON line:
+--dump-outputs DIR: after the timed window, outside its clock, the timed path (Trainer.step) runs
+two more steps on a fresh copy of the seeded starting model, and rank 0 writes what they leave its
+caller as float32 / float64 DIR/<name>.npy: parameters and Adam moments on a fixed, seeded sample
+of rows, the row indices, the step info.  Equal arguments give equal inputs and, to rounding,
+equal outputs; _dump_outputs says what the files carry, why two steps, and the measured noise.
+
+Extra objects on the JSON line (--full):
   roofline      heaviest HBM-bound kernel of the step (HIP events on the launch stream), algorithmic
                 bytes per launch from SURVEY §8(d) x the frame's measured L / V / L_eff / T / N;
                 the VALU-bound blends beside it (blend_fwd / blend_bwd) and the heaviest kernel
@@ -57,6 +68,12 @@ def parse(argv=None):
                         "a child and exits with its code; under a launcher it must equal WORLD_SIZE")
     p.add_argument("--steps", type=int, default=100)
     p.add_argument("--warmup", type=int, default=10)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, run the timed path's step twice more on the seeded starting model "
+                        "and write the results (sampled parameter rows, Adam moments, step info) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beside the headline figure: stage profile and roofline, densify "
+                        "cost, loss read-back / bracket / reference-API legs, forward throughput, CPU baseline")
     p.add_argument("--points", type=int, default=1_000_000)
     p.add_argument("--width", type=int, default=1920)
     p.add_argument("--height", type=int, default=1080)
@@ -65,7 +82,8 @@ def parse(argv=None):
     p.add_argument("--fwd-frames", type=int, default=50)
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-threads", type=int, default=0)
-    p.add_argument("--no-profile", action="store_true", help="skip HIP-event stage timing in the timed region")
+    p.add_argument("--no-profile", action="store_true", help="with --full: skip the HIP-event stage timing, the profiled window's iterations "
+                                                                 "included (no effect on a plain run)")
     p.add_argument("--aux-normal", action="store_true",
                    help="forward-only leg renders the aux depth + normal outputs (BASELINE configs[4] stress)")
     p.add_argument("--binning-split", type=int, default=0,
@@ -242,9 +260,11 @@ def main():
                       exchange=True if force else None)
 
     K, Wm = args.steps, args.warmup
-    prof = not args.no_profile
-    # untimed per-stage breakdown window (every stage event-timed) between warmup and the timed loop
-    PW = min(20, K) if prof else 0
+    full = args.full
+    prof = full and not args.no_profile
+    # untimed per-stage breakdown window (every stage event-timed with --full) between warmup and the
+    # timed loop; a plain run steps through the same iterations, so both time the same model state
+    PW = min(20, K) if prof or not full else 0
     D0, D1 = 900, 1000  # densify/prune iterations (train.py:136-140: multiples of 100 in (500, 15000))
     for it in range(D0 - Wm + 1, D0 + 1):
         trainer.step(it)
@@ -265,18 +285,24 @@ def main():
         step_dom = max(modeled, key=lambda k: breakdown[k][0]) if modeled else None
         hbm_bound = [k for k in modeled if k not in VALU_BOUND]
         dom = max(hbm_bound, key=lambda k: breakdown[k][0]) if hbm_bound else step_dom
-    # one ordinary and one densify/prune iteration, each alone between device syncs
+    else:
+        for _ in range(PW):
+            trainer.step(it)
+            it += 1
+    # one ordinary and one densify/prune iteration, with --full each alone between device syncs
     one_ms = {}
     for it in (D1 - 1, D1):
-        torch.cuda.synchronize()
-        if world > 1:
-            dist.barrier()
-        t0 = time.perf_counter()
+        if full:
+            torch.cuda.synchronize()
+            if world > 1:
+                dist.barrier()
+            t0 = time.perf_counter()
         info = trainer.step(it)
-        torch.cuda.synchronize()
-        one_ms[it] = 1000.0 * (time.perf_counter() - t0)
+        if full:
+            torch.cuda.synchronize()
+            one_ms[it] = 1000.0 * (time.perf_counter() - t0)
     assert info.densified, "iteration 1000 must densify"
-    if world > 1:
+    if full and world > 1:
         e = torch.tensor([one_ms[D1 - 1], one_ms[D1]], device=dev, dtype=torch.float64)
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
         one_ms = {D1 - 1: float(e[0]), D1: float(e[1])}
@@ -322,6 +348,36 @@ def main():
     trainer.sync_state()
     end_iter = it - 1
     n_densify = sum(1 for i in range(start_iter, end_iter + 1) if i % 100 == 0)
+    if args.dump_outputs:  # every rank steps; rank 0 writes
+        _dump_outputs(args.dump_outputs, args, cams, gts, opt, pipe, extent, start_iter, rank, force, dev)
+    line = {
+        "metric": "train iters/sec + forward Mpix/sec, 1M Gaussians @ 1080p, 1/2/4/8 MI355X",
+        "value": round(iters_per_s, 3),
+        "unit": "train iters/s",
+        "n_gpus": world,
+        "steps": K,
+        "warmup": Wm,
+        "ms_per_step": round(ms_per_step, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "fp32",
+        "data": "synthetic (seeded random Gaussians, 200 Fibonacci-sphere cameras, GT = render of a second random model)",
+        "config": {"workload": f"train.py iteration (render fwd + L1/SSIM + bwd + densify stats + "
+                               f"densify/prune every 100 it + Adam), {P} Gaussians, {W}x{H}, SH {D}, "
+                               f"view-sharded dp{world}",
+                   "gaussians": P, "width": W, "height": H, "sh_degree": D, "views": args.views,
+                   "parallelism": (f"dp{world} (view-parallel, Gaussian-sharded: RCCL all-to-all of per-view "
+                                   f"records)" if world > 1 else "dp1 (RCCL exchange forced)" if force else "dp1"),
+                   "iterations": [start_iter, end_iter], "densify_events_in_window": n_densify},
+    }
+    if not full:
+        if rank == 0:
+            os.write(out_fd, (json.dumps(line) + "\n").encode())
+        if world > 1 or force:
+            dist.destroy_process_group()
+        return 0
+
     densify_extra_ms = one_ms[D1] - one_ms[D1 - 1]
     # the reference's share (1 densify/prune iteration in 100) on top of the measured steps
     ms_1in100 = ms_per_step + densify_extra_ms / 100.0 if n_densify == 0 else ms_per_step
@@ -455,30 +511,11 @@ def main():
     if world > 1:
         dist.barrier()
 
-    line = {
-        "metric": "train iters/sec + forward Mpix/sec, 1M Gaussians @ 1080p, 1/2/4/8 MI355X",
-        "value": round(iters_per_s, 3),
+    line.update({
         # the reference loop's densify/prune share (1 iteration in 100) priced in: the measured window
         # when it holds one, else the ordinary steps plus 1/100 of the measured extra cost of a
         # densify iteration (densify_iter_ms - ordinary_iter_ms_alone)
         "iters_per_s_1in100": round(world * 1000.0 / ms_1in100, 3),
-        "unit": "train iters/s",
-        "n_gpus": world,
-        "steps": K,
-        "warmup": Wm,
-        "ms_per_step": round(ms_per_step, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "fp32",
-        "data": "synthetic (seeded random Gaussians, 200 Fibonacci-sphere cameras, GT = render of a second random model)",
-        "config": {"workload": f"train.py iteration (render fwd + L1/SSIM + bwd + densify stats + "
-                               f"densify/prune every 100 it + Adam), {P} Gaussians, {W}x{H}, SH {D}, "
-                               f"view-sharded dp{world}",
-                   "gaussians": P, "width": W, "height": H, "sh_degree": D, "views": args.views,
-                   "parallelism": (f"dp{world} (view-parallel, Gaussian-sharded: RCCL all-to-all of per-view "
-                                   f"records)" if world > 1 else "dp1 (RCCL exchange forced)" if force else "dp1"),
-                   "iterations": [start_iter, end_iter], "densify_events_in_window": n_densify},
         # the timed step plus the reference's per-iteration `loss.item()` host read-back (train.py:120)
         "sync_loss_iters_per_s": round(world * 1000.0 / sync_ms, 3),
         "sync_loss_ms_per_step": round(sync_ms, 4),
@@ -510,11 +547,82 @@ def main():
         "kernels": kernels,
         "kernels_window": f"{PW} untimed profiled iterations between warmup and the timed loop (all stages event-timed)",
         "cpu_baseline": cpu,
-    }
+    })
     if rank == 0:
         os.write(out_fd, (json.dumps(line) + "\n").encode())
     if world > 1 or force:
         dist.destroy_process_group()
+
+
+DUMP_ROWS = 16384  # x (55 parameter floats + 2 x 55 moment floats) x 4 B = 11 MB
+
+
+def _dump_outputs(path, args, cams, gts, opt, pipe, extent, iteration, rank, force, dev):
+    """Two more consecutive steps of the timed path (Trainer.step, iterations `iteration` and
+    `iteration` + 1), after the clock has stopped, on a fresh copy of the benchmark's seeded starting
+    model with a new optimizer, and what they leave their caller as float32 / float64 .npy files:
+    the parameter arrays and their Adam moments on DUMP_ROWS rows drawn with a fixed seed (sorted, in
+    rows.npy; every row of a smaller model), and the second step's StepInfo.
+
+    Why two steps: the first renders through the ordinary preprocess; its per-Gaussian backward also
+    writes the next frame's geometry (rr_next_frame), and the second renders from that, as every
+    timed step but the first after a densify does.  So the moments depend on both forward paths.
+    Why not the model the timed window ends in: the blend backward adds with float atomics in launch
+    order, and the hundred-odd optimizer steps before it amplify those last bits (two runs of one
+    build: relative L1 1e-5 on xyz, 2e-3 on features_dc, up to 3e-2 on the moments).
+    What the files carry: after two Adam steps from zero moments a parameter has moved by about
+    lr x (sign(g1) + a ratio of g1 and g2 near +-1), nearly whatever the gradients' size, so the
+    parameter files say little more than the gradients' signs; the gradients g1, g2 themselves are in
+    the moments (exp_avg = 0.09 g1 + 0.1 g2, exp_avg_sq = 0.000999 g1^2 + 0.001 g2^2).
+    The rotations are held (learning rate 0 in this model's optimizer) and left out of the files:
+    the starting model's scales are isotropic (synthetic.init_scales), so the covariance does not
+    depend on the rotation, its first gradient is zero analytically and 1e-13 of rounding in the
+    kernels, and Adam's first step would turn the sign of that rounding into +- the learning rate:
+    a random rotation of 1e-3 per run, which the second step, whose scales are no longer isotropic,
+    renders (measured with the rotations stepping: 3e-4 relative L1 between runs on the scaling
+    moments, 4e-6 or less on the others).
+    Run-to-run noise of these files, measured on one build at the default size (three runs):
+    relative L1 2e-9 or less on the parameters, 2.1e-7 or less on the moments; no element further
+    apart than 1e-5 of its value + 1e-6 of its array's largest."""
+    import numpy as np
+    import torch
+
+    from rain_amd import synthetic
+    from rain_amd.gaussian_model import GaussianModel
+    from rain_amd.train import TrainConfig, Trainer
+
+    D = args.sh_degree
+    g = GaussianModel(D, divide_ratio=0.8, device=dev)
+    g.set_params(synthetic.random_gaussians(args.points, sh_degree=D, seed=0, bench=True, device=dev))
+    g.active_sh_degree = D
+    g.spatial_lr_scale = extent
+    g.training_setup(opt)
+    for group in g.optimizer.param_groups:  # see the docstring: the first rotation gradient is rounding only
+        if group["name"] == "rotation":
+            group["lr"] = 0.0
+    tr = Trainer(g, cams, gts, opt, pipe, TrainConfig(seed=0), scene_extent=extent, exchange=True if force else None)
+    for it in (iteration, iteration + 1):
+        info = tr.step(it)
+    torch.cuda.synchronize()
+    tr.sync_state()
+    if rank != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    n = g.get_xyz.shape[0]
+    rows = np.arange(n) if n <= DUMP_ROWS else np.sort(np.random.default_rng(0).choice(n, DUMP_ROWS, replace=False))
+    idx = torch.from_numpy(rows).to(dev)
+    names = ("xyz", "features_dc", "features_rest", "opacity", "scaling", "rotation")
+    out = {"rows": rows.astype(np.float64),
+           "step_info": np.array([iteration + 1, info.view, info.low_pass, info.num_gaussians], dtype=np.float64)}
+    for name, p in zip(names, g.params()):
+        if name == "rotation":
+            continue
+        out[name] = p.detach()[idx].float().cpu().numpy()
+        state = g.optimizer.state[p]
+        for key in ("exp_avg", "exp_avg_sq"):
+            out[f"{name}_{key}"] = state[key].detach()[idx].float().cpu().numpy()
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 def _clear_window(start, n):

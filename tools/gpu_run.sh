@@ -8,7 +8,8 @@
 # STEP is one of
 #   smoke                 __graft_entry__.smoke()
 #   tests[=EXPR]          pytest -m gpu (EXPR: a -k expression)
-#   bench[=ARGS]          python bench.py ARGS (default: the driver's command line)
+#   bench[=ARGS]          python bench.py ARGS (default: a short --full run, every leg on the line;
+#                         bench='--gpus 1 --steps N --warmup W' is the plain run of the headline figure)
 #   ab=T1,T2[,..]         interleaved A/B of the training step (tools/variant_step.py), two rounds;
 #                         Ti = a list of rr_set_tuning key=value (or variant_step.py --options)
 #                         joined by '+', or 'base'
@@ -39,7 +40,7 @@ for STEP in "$@"; do
         > ${OUT}_gpu_tests.log 2>&1; rc=$?; tail -3 ${OUT}_gpu_tests.log
       [ $rc -eq 0 ] || { grep -E "FAIL|Error|error" ${OUT}_gpu_tests.log | head -30; exit $rc; } ;;
     bench|bench=*)
-      A="--gpus 1 --steps 20 --warmup 5"; [ "$STEP" != bench ] && A="${STEP#bench=}"
+      A="--gpus 1 --steps 20 --warmup 5 --full"; [ "$STEP" != bench ] && A="${STEP#bench=}"
       timeout -k 10 600 python3 bench.py $A > ${OUT}_bench.json 2> ${OUT}_bench.err \
         || { tail -20 ${OUT}_bench.err; exit 1; }
       cat ${OUT}_bench.json ;;
@@ -115,7 +116,7 @@ for STEP in "$@"; do
       # child under the profiler
       A=""; [ "$STEP" != prof ] && A="${STEP#prof=}"
       RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29531 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d ${OUT}_prof -o run --output-format csv \
-        -- python3 bench.py --no-cpu-baseline $A > ${OUT}_prof_bench.json 2> ${OUT}_prof.err \
+        -- python3 bench.py --full --no-cpu-baseline $A > ${OUT}_prof_bench.json 2> ${OUT}_prof.err \
         || { tail -20 ${OUT}_prof.err; exit 1; }
       python3 tools/step_breakdown.py ${OUT}_prof --window > ${OUT}_timed_kernels.txt 2>&1
       python3 tools/step_breakdown.py ${OUT}_prof --window --seq | tail -40 > ${OUT}_launch_sequence.txt 2>&1

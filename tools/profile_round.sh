@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 mkdir -p "$OUT"
 if [ "$2" != pmc-only ]; then
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/bench" -o run --output-format csv \
-    -- python3 bench.py --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err"
+    -- python3 bench.py --full --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err"
 fi
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$OUT/pmc_fetch" -o run --output-format csv \
     -- python3 tools/pmc_workload.py > "$OUT/fetch.log" 2>&1
