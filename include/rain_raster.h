@@ -137,7 +137,8 @@ int rr_forward_geometry(const rr_frame* f, const rr_camera* cam, const rr_gaussi
  * each bin's pairs in the reference's (depth, index) order, split them into the bin's tile lists
  * and ranges, and alpha-blend every tile (two early-stop phases on large frames).
  * out_color [3,H,W], out_depth [1,H,W] are fully written.  `f` must carry the same flags as in
- * stage 1.
+ * stage 1.  Exactly one render per rr_forward_geometry / rr_forward_from_geometry, into the same
+ * image buffer, on the same host thread: any other render fails with RR_ERR_ARG.
  */
 int rr_forward_render(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
                       void* geom_buffer, void* image_buffer, void* binning_buffer, size_t binning_bytes,
@@ -300,7 +301,8 @@ int rr_unpack_rows(int world, int rows_per_rank, const void* recv, size_t chunk_
 /* rr_forward over a geometry buffer whose preprocess arrays are already filled (frame.P rows;
  * radii [P]) — by the sharded step's unpack or by the previous step's backward (rr_next_frame);
  * same outputs, same RR_INCOMPLETE / binning_needed protocol, with rr_forward_render_geometry as the
- * second stage. */
+ * second stage.  Exactly one render per rr_forward_geometry / rr_forward_from_geometry, into the
+ * same image buffer, on the same host thread (as for rr_forward_render). */
 int rr_forward_from_geometry(const rr_frame* f, const rr_camera* cam, const int* radii, void* geom_buffer,
                              size_t geom_bytes, void* image_buffer, size_t image_bytes, void* binning_buffer,
                              size_t binning_bytes, int* num_rendered, int* num_pairs, size_t* binning_needed,

@@ -1,20 +1,23 @@
-// rr_api.hip — C-ABI entry points (include/rain_raster.h): scratch carving, stage ordering,
-// the single device->host sync, debug checks and event timing.
+// rr_api.hip — the C-ABI entry points of the render path (include/rain_raster.h): forward,
+// backward and the Gaussian-sharded step; stage ordering, the single device->host sync and the
+// hand-off between a frame's forward and its backward; then runtime tuning, frame statistics, debug
+// views and the per-stage profile.  The scratch layout is rr_layout.hpp.
 //
 // Replaces CudaRasterizer::Rasterizer::{forward,backward,markVisible}
 // (rasterizer_impl.cu:130-142,187-430) and the pybind wrappers (rasterize_points.cu:24-212).
 #include <algorithm>
 #include <chrono>
-#include <cstdio>
 #include <cstring>
 #include <deque>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/rain_raster.h"
 #include "rr_common.hpp"
 #include "rr_kernels.hpp"
+#include "rr_layout.hpp"
 
 using namespace rr;
 
@@ -34,226 +37,11 @@ Tuning& tuning() {
 
 namespace {
 
-thread_local std::string g_err;
+thread_local std::string g_err;  // rr_last_error
 
 int fail(int code, const std::string& msg) {
     g_err = msg;
     return code;
-}
-
-constexpr size_t kAlign = 256;
-inline size_t align_up(size_t x) { return (x + kAlign - 1) & ~(kAlign - 1); }
-
-// Bump allocator over an opaque byte buffer (rasterizer_impl.h:10-16 `obtain`).
-struct Carver {
-    char* base;
-    size_t off = 0;
-    explicit Carver(void* b) : base(static_cast<char*>(b)) {}
-    template <typename T>
-    T* take(size_t n) {
-        off = align_up(off);
-        T* p = reinterpret_cast<T*>(base ? base + off : nullptr);
-        off += n * sizeof(T);
-        return p;
-    }
-};
-
-// rasterizer_impl.cu:24-39
-uint32_t higher_msb(uint32_t n) {
-    uint32_t msb = sizeof(n) * 4;
-    uint32_t step = msb;
-    while (step > 1) {
-        step /= 2;
-        if (n >> msb) msb += step;
-        else msb -= step;
-    }
-    if (n >> msb) msb++;
-    return msb;
-}
-
-inline int grid_x(int W) { return (W + TILE_X - 1) / TILE_X; }
-inline int grid_y(int H) { return (H + TILE_Y - 1) / TILE_Y; }
-
-
-// ---- scratch layouts ----
-struct Geom {
-    Splat* splats;
-    uint2* tiles;         // per Gaussian {pairs emitted, bounding-rect tiles}
-    uint32_t* depth_keys;
-    PhaseLists lists;     // the early-stop phases' Gaussians in index order with their pair offsets
-    float4* normals;      // RR_FLAG_AUX_NORMAL: view-space normal per visible Gaussian
-    uint2* block_sums;    // [ceil(P/256)] per-preprocess-block sums of tiles[] (pairs, rect tiles)
-    uint32_t* block_wide; // [ceil(P/256)] per block: a visible depth key needs more than kDepthKeyBits
-    FrameTotals* ft;      // the frame's counts and early-stop depth cut (rr_bin.hip)
-    void* temp;           // the pair scan's block totals
-    size_t temp_bytes;
-    size_t total;
-};
-Geom carve_geom(void* buf, int P) {
-    Carver c(buf);
-    Geom g;
-    const size_t n = (size_t)std::max(P, 1);
-    g.splats = c.take<Splat>(n);
-    g.tiles = c.take<uint2>(n);
-    g.depth_keys = c.take<uint32_t>(n);
-    g.lists.idx_a = c.take<uint32_t>(n);
-    g.lists.off_a = c.take<uint32_t>(n);
-    g.lists.idx_b = c.take<uint32_t>(n);
-    g.lists.off_b = c.take<uint32_t>(n);
-    // window starts for up to 2048 * P / 16 pairs per phase (more: a window-starts launch)
-    g.lists.nwin = (uint32_t)std::min<size_t>(std::max<size_t>(n / 16, 64), (1u << 29) / kSplitWin + 1);
-    g.lists.first_a = c.take<uint32_t>(g.lists.nwin);
-    g.lists.first_b = c.take<uint32_t>(g.lists.nwin);
-    g.normals = c.take<float4>(n);
-    g.block_sums = c.take<uint2>((n + 255) / 256);
-    g.block_wide = c.take<uint32_t>((n + 255) / 256);
-    g.ft = c.take<FrameTotals>(1);
-    g.temp_bytes = split_scan_temp_bytes(P);
-    g.temp = c.take<char>(std::max<size_t>(g.temp_bytes, 1));
-    g.total = align_up(c.off);
-    return g;
-}
-
-struct Img {
-    float* final_T;
-    uint32_t* n_contrib;
-    uint2* ranges;      // phase-A (or single-phase) lists; ranges_b and counters follow it
-    uint2* ranges_b;    // phase-B lists of early-stop binning (all {0,0} otherwise)
-    uint32_t* counters; // [0] phase-B pairs (gather path: slots reserved), [1] backward tile order done,
-                        // [2] phase B took the gather path, [3] phase-B pairs its bin runs hold
-    size_t zero_bytes;  // ranges .. bin_cnt_a: cleared before every render
-    uint32_t* tile_max;
-    uint8_t* open;      // [T] tile still open after phase A
-    uint32_t* open_bits;  // [ceil(T/32)] open as a bitmask (in the zeroed block; the phase-A blend sets it)
-    uint2* bounds_a;      // [bins] phase A's (or the single phase's) bin runs (zeroed block; k_bin_bounds)
-    uint2* bounds_b;      // [bins] phase B's
-    uint32_t* bin_cnt;    // [2 bins] phase B's pair count per bin (the gather path), then its fill
-    uint32_t* bin_cnt_a;  // [2 bins] phase A's
-    uint32_t* order;      // [T] backward blend dispatch order (heaviest tiles first)
-    size_t total;
-};
-Img carve_img(void* buf, int W, int H) {
-    Carver c(buf);
-    Img m;
-    const size_t N = (size_t)std::max(W * H, 1);
-    const size_t T = (size_t)std::max(grid_x(W) * grid_y(H), 1);
-    m.final_T = c.take<float>(N);
-    m.n_contrib = c.take<uint32_t>(N);
-    // one block, cleared before every render: ranges [T], ranges_b [T], counters [4],
-    // open_bits [ceil(T/32)], bounds_a [bins], bounds_b [bins], bin_cnt [2 bins], bin_cnt_a [2 bins]
-    const size_t nbits = ((size_t)T + 31) / 32;
-    const size_t NB = (size_t)std::max(bins_x(grid_x(W)) * bins_y(grid_y(H)), 1);
-    const size_t nz = 2 * (size_t)T + 2 + (nbits + 1) / 2 + 2 * NB + 2 * NB;
-    m.ranges = c.take<uint2>(nz);
-    m.ranges_b = m.ranges ? m.ranges + T : nullptr;
-    m.counters = m.ranges ? reinterpret_cast<uint32_t*>(m.ranges + 2 * T) : nullptr;
-    m.open_bits = m.ranges ? reinterpret_cast<uint32_t*>(m.ranges + 2 * T + 2) : nullptr;
-    m.bounds_a = m.ranges ? m.ranges + 2 * T + 2 + (nbits + 1) / 2 : nullptr;
-    m.bounds_b = m.ranges ? m.bounds_a + NB : nullptr;
-    m.bin_cnt = m.ranges ? reinterpret_cast<uint32_t*>(m.bounds_b + NB) : nullptr;
-    m.bin_cnt_a = m.ranges ? m.bin_cnt + 2 * NB : nullptr;
-    m.zero_bytes = nz * sizeof(uint2);
-    m.tile_max = c.take<uint32_t>(T);
-    m.open = c.take<uint8_t>(T);
-    m.order = c.take<uint32_t>(T);
-    m.total = align_up(c.off);
-    return m;
-}
-
-// Early-stop binning split (rr_bin.hip depth_cut): phase A bins the pairs of the Gaussians nearer
-// than a per-frame depth cut holding ~1/den of the pairs, for every tile; phase B the rest, only for
-// the tiles phase A left open (rr_kernels.hpp BlendPhase).  den = 3: on the bench frames (1M
-// Gaussians, 1080p) most tiles saturate inside the first third (tools/saturation_stats.py; with the
-// depth-rank split of rounds 1-3, tools/step_ab.py --split 2,3,4: 1.509 / 1.491 / 1.525 ms per
-// step).  Frames below Tuning::early_min pairs are binned in one phase.  rr_set_binning_config
-// changes both (tests force the split onto small frames).
-//
-// Binning paths: phase A (or the single phase) by the windowed duplicate over the split scan's
-// index-ordered list + the stable bin sort; phase B by the gather path (rr_forward.hip k_dup_gather,
-// per-bin count / scatter: few pairs) when the grid's bins fit one workgroup's count (rr_bin.hip
-// kBinScanMax), else by the windowed path (Tuning::b_gather off forces it onto small frames).
-constexpr int kGatherMaxBins = 16384;  // rr_bin.hip kBinScanMax
-bool b_gather(int W, int H) {
-    return tuning().b_gather && bins_x(grid_x(W)) * bins_y(grid_y(H)) <= kGatherMaxBins;
-}
-
-struct Bin {
-    // FIRST, so the backward finds it without knowing the pair count: the per-tile lists
-    // k_sortexpand writes, 4 slots per (bin, Gaussian) pair.  The host knows only the frame's
-    // total L (the phases' split LA + LB = L stays on the device).  Every pair array has a phase-A
-    // region [0, L) and a phase-B region [L, 2L) (point_list: [0, 4L) and [4L, 8L)), plus the bin
-    // sort's arrays — 56 B per pair with 16-bit bin keys (point_list 32, keys 4 + 4 sorted, values
-    // 8 + 8 sorted) + ~0.5 B of sort counts.
-    // Bins of more than 2048 pairs are depth-sorted inside their own point_list region (rr_bin.hip
-    // sortexpand_run): no scratch arrays.
-    uint32_t* point_list;
-    void* keys;            // bin ids of the (bin, Gaussian) pairs
-    void* keys_sorted;
-    uint32_t* vals;        // Gaussian | tile mask << BIN_SHIFT, then sorted
-    uint32_t* vals_sorted;
-    uint32_t* first;       // first Gaussian of every duplicate window (= sort unit), phase A then B
-    uint32_t* unit_len;    // phase B: pairs kept per window
-    void* temp;            // bin-sort scratch, shared by the two phases
-    size_t temp_bytes;
-    bool wide;  // 32-bit bin keys (more than 65536 bins)
-    int bits;
-    uint32_t L;  // (bin, Gaussian) pairs of both phases
-    size_t total;
-};
-// Window (= sort unit) length of each phase's sort, chosen for the pairs it is expected to hold
-// (the split scan's depth cut aims phase A at ~1/den of the pairs) while its windows cover the
-// capacity L.
-struct PhaseHints {
-    size_t a, b;
-};
-PhaseHints phase_hints(uint32_t L, bool early) {
-    const size_t n = std::max<size_t>(L, 1);
-    const size_t a = std::max<size_t>(n / std::max<uint32_t>(tuning().early_den, 1u), 1);
-    return early ? PhaseHints{a, std::max<size_t>(n - a, 1)} : PhaseHints{n, n};
-}
-template <typename K>
-RadixPlan tile_plan(void* temp, uint32_t n, int bits, size_t hint) {
-    return radix_sort_plan<K>(temp, (size_t)n, 0, bits, hint);
-}
-// The layout depends on the frame's pair count L only, sized for the early-stop split (its
-// phase-A hint has the most windows; a single-phase frame uses fewer).
-Bin carve_bin(void* buf, int L, int W, int H) {
-    Carver c(buf);
-    Bin b;
-    const int NB = bins_x(grid_x(W)) * bins_y(grid_y(H));
-    b.wide = NB > 65536 || tuning().wide_bin_keys;
-    b.bits = std::max(1, (int)higher_msb((uint32_t)NB));  // >= 1: the duplicate windows are sort units
-    b.L = (uint32_t)std::max(L, 0);
-    const size_t np = 2 * (size_t)std::max(L, 1);  // entries of each pair array: both phases' regions
-    b.point_list = c.take<uint32_t>(4 * np + kPointListPad);
-    if (b.wide) {
-        b.keys = c.take<uint32_t>(np);
-        b.keys_sorted = c.take<uint32_t>(np);
-    } else {
-        b.keys = c.take<uint16_t>(np);
-        b.keys_sorted = c.take<uint16_t>(np);
-    }
-    b.vals = c.take<uint32_t>(np);
-    b.vals_sorted = c.take<uint32_t>(np);
-    {
-        const PhaseHints h = phase_hints(b.L, true);
-        auto units = [&](size_t hint) {
-            return b.wide ? tile_plan<uint32_t>(nullptr, b.L, b.bits, hint).units
-                          : tile_plan<uint16_t>(nullptr, b.L, b.bits, hint).units;
-        };
-        const int ua = std::max(units(h.a), 1), ub = std::max(units(h.b), 1);
-        b.first = c.take<uint32_t>((size_t)ua + ub + 2);
-        b.unit_len = c.take<uint32_t>((size_t)ub + 1);
-        auto temp = [&](size_t hint) {
-            return b.L == 0 ? (size_t)0
-                   : b.wide ? radix_sort_temp_bytes<uint32_t>(b.L, b.bits, hint)
-                            : radix_sort_temp_bytes<uint16_t>(b.L, b.bits, hint);
-        };
-        b.temp_bytes = std::max(temp(h.a), temp(h.b));
-        b.temp = c.take<char>(std::max<size_t>(b.temp_bytes, 1));
-    }
-    b.total = align_up(c.off);
-    return b;
 }
 
 // ---- event timing (bench.py reads per-stage kernel time through rr_profile_collect) ----
@@ -323,6 +111,15 @@ int check(const rr_frame* f, hipStream_t st, const char* what) {
         int _rc = check(f, st, what);          \
         if (_rc != RR_OK) return _rc;          \
     } while (0)
+// One stage whose launches cannot fail on the host: `launch` between the stage's events, then its check.
+template <typename F>
+int stage(const rr_frame* f, hipStream_t st, int id, const char* what, F&& launch) {
+    {
+        StageTimer tm(id, st);
+        launch();
+    }
+    return check(f, st, what);
+}
 
 // ---------------------------------------------------------------------------------------
 // Readback of the forward's pair counts.  A hipMemcpyAsync into pageable host memory + stream
@@ -331,9 +128,9 @@ int check(const rr_frame* f, hipStream_t st, const char* what) {
 // (rr_bin.hip k_split_scan_totals: workgroup 0, once the frame's totals and depth cut are known;
 // the scan runs on while the host reads) stores the counts and a sequence number into a coherent
 // pinned host mailbox (system-scope stores, the sequence number last) and the host thread spins on
-// the sequence number.  Once the
-// wait has outlasted any frame the stream is queried: a launch / kernel error is reported, and a
-// stream that went idle without the sequence number becoming visible falls back to the plain copy.
+// the sequence number.  Once the wait has outlasted any frame the stream is queried: a launch /
+// kernel error is reported, and a stream that went idle without the sequence number becoming
+// visible falls back to the plain copy.
 struct Mailbox {
     uint32_t* host = nullptr;  // [L, rect, seq, wide], coherent pinned
     uint32_t* dev = nullptr;   // device alias of host
@@ -383,7 +180,7 @@ hipError_t pair_counts_copy(const FrameTotals* src, PairCounts* out, hipStream_t
     return e;
 }
 
-thread_local int64_t g_wait_ns = 0, g_waits = 0;
+thread_local int64_t g_wait_ns = 0, g_waits = 0;  // rr_host_wait_stats
 #ifndef RR_WAIT_QUERY_MS
 #define RR_WAIT_QUERY_MS 20
 #endif
@@ -422,6 +219,7 @@ hipError_t pair_counts_wait(const PairCountRead& r, PairCounts* out, hipStream_t
     }
 }
 
+// ---- argument checks and the argument blocks several entry points fill ----
 int validate(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, bool forward) {
     if (!f || !cam || !g) return fail(RR_ERR_ARG, "null frame/camera/gaussians");
     if (f->P < 0 || f->width <= 0 || f->height <= 0) return fail(RR_ERR_ARG, "bad P/width/height");
@@ -449,6 +247,33 @@ int validate(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, boo
     return RR_OK;
 }
 
+int check_views(const rr_view* views, int num_views) {
+    for (int v = 0; v < num_views; v++) {
+        const rr_view& w = views[v];
+        if (!w.viewmatrix || !w.projmatrix || !w.campos || w.width <= 0 || w.height <= 0)
+            return fail(RR_ERR_ARG, "bad view");
+    }
+    return RR_OK;
+}
+
+// focal length in pixels of an image `extent` pixels wide (high) with half-angle tangent tan_half
+inline float focal(int extent, float tan_half) { return extent / (2.0f * tan_half); }
+
+// The fused optimizer step's groups: moments present and param the matching input array, for every
+// group (all_stepped: a group without param is an error) or for the groups that have a param.
+// f_rest does not exist when M <= 1.
+int check_adam(const rr_frame* f, const rr_gaussians* g, const rr_adam* ad, bool all_stepped) {
+    const rr_adam_group* gs[6] = {&ad->xyz, &ad->f_dc, &ad->f_rest, &ad->opacity, &ad->scaling, &ad->rotation};
+    const void* in[6] = {g->means3D, g->shs, g->shs_rest, g->opacities, g->scales, g->rotations};
+    for (int i = 0; i < 6; i++) {
+        if ((i == 2 && f->M <= 1) || (!all_stepped && !gs[i]->param)) continue;
+        if (!gs[i]->param || !gs[i]->exp_avg || !gs[i]->exp_avg_sq)
+            return fail(RR_ERR_ARG, all_stepped ? "null Adam group array" : "null Adam moment array");
+        if (gs[i]->param != in[i]) return fail(RR_ERR_ARG, "Adam group param must be the matching input array");
+    }
+    return RR_OK;
+}
+
 // Preprocess arguments of a frame (the output arrays are set by the caller).
 PreArgs pre_args(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g) {
     PreArgs a{};
@@ -456,8 +281,8 @@ PreArgs pre_args(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g)
     a.gx = grid_x(f->width); a.gy = grid_y(f->height);
     a.prefiltered = f->prefiltered;
     a.tanfovx = f->tan_fovx; a.tanfovy = f->tan_fovy;
-    a.focal_y = f->height / (2.0f * f->tan_fovy);
-    a.focal_x = f->width / (2.0f * f->tan_fovx);
+    a.focal_y = focal(f->height, f->tan_fovy);
+    a.focal_x = focal(f->width, f->tan_fovx);
     a.scale_modifier = f->scale_modifier; a.low_pass = f->low_pass;
     a.means3D = g->means3D; a.shs = g->shs; a.colors_precomp = g->colors_precomp; a.opacities = g->opacities;
     a.scales = g->scales; a.rotations = g->rotations; a.cov3D_precomp = g->cov3D_precomp;
@@ -468,10 +293,85 @@ PreArgs pre_args(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g)
     return a;
 }
 
-// The image buffer whose per-frame block the last pair count of this thread cleared, not yet
-// rendered into: a render consumes it, so that a second render after one pair count (whose gather
-// counters would start where the first one's ended, past their regions) fails instead.
-thread_local const void* g_counted_img = nullptr;
+// The per-Gaussian backward's arguments that do not depend on the camera(s) or on gradient arrays.
+GaussBwdArgs gauss_bwd_args(const rr_frame* f, const rr_gaussians* g, const rr_grads* out) {
+    GaussBwdArgs a{};
+    a.P = f->P; a.D = f->D; a.M = f->M;
+    a.scale_modifier = f->scale_modifier;
+    a.means3D = g->means3D; a.shs = g->shs; a.scales = g->scales; a.rotations = g->rotations;
+    a.raw = (f->flags & RR_FLAG_RAW_PARAMS) ? 1 : 0; a.opacities = g->opacities; a.shs_rest = g->shs_rest;
+    a.grad_accum = out->grad_accum; a.denom = out->denom; a.max_radii2D = out->max_radii2D;
+    a.use_adam = out->adam ? 1 : 0;
+    if (out->adam) a.adam = *out->adam;  // by value: the kernel must not dereference host memory
+    return a;
+}
+
+// ---- the hand-off between a pair count, its render and the frame's backward ----
+// One render per pair count, into the image buffer the count cleared, on the same thread; the
+// workspace registered for the next render is consumed by that render (which zero-fills it inside
+// its first blend launch); what the render leaves for its frame's backward is taken by the first
+// backward of that image buffer.
+struct WsRange {
+    void* ptr = nullptr;
+    size_t bytes = 0;
+};
+// What a render leaves for its frame's backward, which may run on another host thread (autograd's
+// device thread): the workspace it zero-filled, and the backward's tile order when its phase-B
+// duplicate launch computed it (the order array).  A backward whose workspace is the clean one
+// skips its clear, and with the order ready it needs no prologue at all.
+struct FrameFacts {
+    const void* img = nullptr;
+    WsRange clean;
+    const uint32_t* order = nullptr;
+};
+struct Handoff {
+    // This thread's.  counted_img: the image buffer whose per-frame block the last pair count
+    // cleared, not yet rendered into (a second render after one pair count, whose gather counters
+    // would start where the first one's ended, past their regions, fails instead).
+    const void* counted_img = nullptr;
+    WsRange fwd_ws;    // rr_set_forward_workspace: the backward's accumulators, for the next render
+    FrameFacts facts;  // of the render in progress
+    // Process-wide, keyed by the image buffer: the last few renders' facts.  The first backward of
+    // a frame consumes its entry (a second one, of a retained graph, clears and orders by itself).
+    static inline std::mutex mu;
+    static inline std::deque<FrameFacts> published;
+    static constexpr size_t kMaxFacts = 16;
+
+    // false: no pair count of this image buffer to render.  ws: the workspace this render's first
+    // blend launch zero-fills
+    bool begin_render(const void* img, WsRange ws) {
+        if (counted_img != img) return false;
+        counted_img = nullptr;
+        facts = FrameFacts{img, WsRange{}, nullptr};
+        publish();  // drops an earlier render's facts of this buffer
+        facts.clean = ws;
+        return true;
+    }
+    int end_render(int rc) {
+        if (rc == RR_OK) publish();
+        return rc;
+    }
+    static FrameFacts remove(const void* img) {  // with mu held
+        for (auto it = published.begin(); it != published.end(); ++it)
+            if (it->img == img) {
+                const FrameFacts f = *it;
+                published.erase(it);
+                return f;
+            }
+        return FrameFacts{};
+    }
+    void publish() const {
+        std::lock_guard<std::mutex> lk(mu);
+        remove(facts.img);
+        if (facts.clean.ptr || facts.order) published.push_back(facts);
+        if (published.size() > kMaxFacts) published.pop_front();
+    }
+    static FrameFacts take_facts(const void* img) {
+        std::lock_guard<std::mutex> lk(mu);
+        return remove(img);
+    }
+};
+thread_local Handoff g_hand;
 
 // Depth cut + the split pair-count scan -> the one device->host read of the forward, over a
 // geometry buffer whose per-Gaussian arrays (splats, tiles, depth keys, block sums) are filled.  No
@@ -493,7 +393,7 @@ int count_pairs(const rr_frame* f, const Geom& gm, const Img& im, int P, hipStre
                           nzero, ca, st);
         RR_CHECK(hipGetLastError(), "pair-count scan");
     }
-    g_counted_img = im.final_T;
+    g_hand.counted_img = im.final_T;
     RR_STAGE_CHECK("scan");
     // the one device->host sync of the forward (rasterizer_impl.cu:273): pairs to bin, and the
     // reference's num_rendered (sum of bounding-rect areas) which the API returns unchanged; the
@@ -506,93 +406,63 @@ int count_pairs(const rr_frame* f, const Geom& gm, const Img& im, int P, hipStre
     return RR_OK;
 }
 
-}  // namespace
+struct PhaseLabels {
+    const char *dup, *sort_why, *sort, *expand;
+};
+constexpr PhaseLabels kLabelsA{"duplicate", "bin sort (", "bin sort", "sort-expand"};
+constexpr PhaseLabels kLabelsB{"duplicate (phase B)", "bin sort, phase B (", "bin sort (phase B)",
+                               "sort-expand (phase B)"};
+// One phase of the windowed binning path: what differs between phase A (or the only phase) and
+// phase B.
+struct WindowedPhase {
+    uint32_t region;                     // where the phase's region of the pair arrays starts: 0 or L
+    const uint32_t *n_list, *idx, *off;  // its list (PhaseLists) and, on the device, the list's entries (GA / GB)
+    uint32_t* first;                     // its window starts, and whether they are computed already
+    bool starts_done;
+    const uint32_t* L_dev;               // device: the phase's pairs (FrameTotals LA / LB)
+    RadixPlan plan;                      // of its bin sort, chosen for `hint` pairs
+    size_t hint;
+    uint32_t* unit_len;                  // phase B: pairs kept per window (sparse sort units), else null
+    const uint32_t* n_dev;               // device: pairs the bin sort's later passes hold
+    uint2* bounds;                       // the bins' runs
+    uint32_t out_base;                   // where the phase's region of point_list starts
+    uint2* ranges;                       // its tile lists
+    const uint32_t* open_bits;           // phase B: tiles to expand for, else null
+    PhaseLabels what;                    // the stages' names in error messages
+};
 
-extern "C" {
-
-const char* rr_last_error(void) { return g_err.c_str(); }
-const char* rr_version(void) { return "rain_amd-raster 0.1 gfx950"; }
-
-size_t rr_geometry_bytes(int P) { return carve_geom(nullptr, P).total; }
-size_t rr_image_bytes(int width, int height) { return carve_img(nullptr, width, height).total; }
-size_t rr_binning_bytes(int num_rendered, int width, int height) {
-    return carve_bin(nullptr, num_rendered, width, height).total;
-}
-size_t rr_backward_workspace_bytes(int P) { return align_up((size_t)std::max(P, 1) * GACC_STRIDE * sizeof(float)); }
-
-int rr_forward_geometry(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, int* radii, void* geom_buffer,
-                        size_t geom_bytes, void* image_buffer, size_t image_bytes, int* num_rendered,
-                        int* num_pairs, void* stream) {
-    int rc = validate(f, cam, g, true);
-    if (rc) return rc;
-    if (!num_rendered || !num_pairs) return fail(RR_ERR_ARG, "num_rendered / num_pairs is null");
-    *num_rendered = 0;
-    *num_pairs = 0;
-    const int P = f->P, W = f->width, H = f->height;
-    if (P == 0) return RR_OK;
-    if (!radii || !geom_buffer || !image_buffer) return fail(RR_ERR_ARG, "null output buffer");
-    const Geom gm = carve_geom(geom_buffer, P);
-    const Img im = carve_img(image_buffer, W, H);
-    if (geom_bytes < gm.total || image_bytes < im.total) return fail(RR_ERR_CAPACITY, "scratch buffer too small");
-    hipStream_t st = (hipStream_t)stream;
-    PreArgs a = pre_args(f, cam, g);
-    a.radii = radii; a.splats = gm.splats; a.tiles = gm.tiles; a.depth_keys = gm.depth_keys;
-    a.normals = (f->flags & RR_FLAG_AUX_NORMAL) ? gm.normals : nullptr;
-    a.block_sums = gm.block_sums;
-    a.block_wide = gm.block_wide;
+// duplicate -> bin sort -> sort-expand of one phase.  d: the duplicate's arguments that the phases
+// share, and the ones only one of them sets (phase A's second window set, phase B's filter and
+// tile order).  Returns in *starts whether the duplicate computed the window starts.
+template <typename K>
+int windowed_phase(const rr_frame* f, const Geom& gm, const Bin& bn, DupArgs<K>& d, const WindowedPhase& w,
+                   hipStream_t st, bool* starts) {
+    K* keys = static_cast<K*>(bn.keys) + w.region;
+    K* keys_sorted = static_cast<K*>(bn.keys_sorted) + w.region;
+    uint32_t* vals = bn.vals + w.region;
+    uint32_t* vals_sorted = bn.vals_sorted + w.region;
     {
-        StageTimer tm(RR_STAGE_PREPROCESS, st);
-        launch_preprocess(a, st);
+        StageTimer tm(RR_STAGE_DUPLICATE, st);
+        d.n_list = w.n_list; d.idx = w.idx; d.off = w.off; d.first = w.first;
+        d.pair0 = 0; d.win = (uint32_t)w.plan.unit_items; d.nwin = w.plan.units; d.L_dev = w.L_dev;
+        d.keys = keys; d.vals = vals; d.dbits = w.plan.dbits0; d.counts = w.plan.counts;
+        d.unit_len = w.unit_len;
+        d.starts_done = w.starts_done;
+        *starts = launch_duplicate<K>(d, st);
+        d.first_b = nullptr; d.nwin_b = 0; d.starts_done = false;
     }
-    RR_STAGE_CHECK("preprocess");
-    return count_pairs(f, gm, im, P, st, num_rendered, num_pairs);
-}
-
-}  // extern "C"
-
-namespace {
-
-// The backward's accumulator workspace: registered for the next forward render on this thread
-// (rr_set_forward_workspace), which zero-fills it inside its first blend launch.
-struct WsRange {
-    void* ptr = nullptr;
-    size_t bytes = 0;
-};
-thread_local WsRange g_fwd_ws;
-// What a render leaves for its frame's backward, which may run on another host thread (autograd's
-// device thread): the workspace it zero-filled, and the backward's tile order when its phase-B
-// duplicate launch computed it (the order array).  A backward whose workspace is the clean one
-// skips its clear, and with the order ready it needs no prologue at all.  Process-wide, keyed by
-// the image buffer, the last few renders; the first backward of a frame consumes its entry (a
-// second one, of a retained graph, clears and orders by itself).
-struct FrameFacts {
-    const void* img = nullptr;
-    WsRange clean;
-    const uint32_t* order = nullptr;
-};
-std::mutex g_facts_mu;
-std::deque<FrameFacts> g_facts;
-constexpr size_t kMaxFacts = 16;
-thread_local FrameFacts g_render_facts;  // the facts of the render in progress on this thread
-void publish_facts(const FrameFacts& f) {
-    std::lock_guard<std::mutex> lk(g_facts_mu);
-    for (auto it = g_facts.begin(); it != g_facts.end(); ++it)
-        if (it->img == f.img) {
-            g_facts.erase(it);
-            break;
-        }
-    if (f.clean.ptr || f.order) g_facts.push_back(f);
-    if (g_facts.size() > kMaxFacts) g_facts.pop_front();
-}
-FrameFacts take_facts(const void* img) {
-    std::lock_guard<std::mutex> lk(g_facts_mu);
-    for (auto it = g_facts.begin(); it != g_facts.end(); ++it)
-        if (it->img == img) {
-            const FrameFacts f = *it;
-            g_facts.erase(it);
-            return f;
-        }
-    return FrameFacts{};
+    RR_STAGE_CHECK(w.what.dup);
+    {
+        StageTimer tm(RR_STAGE_TILE_SORT, st);
+        RR_CHECK(radix_sort_pairs<K>(bn.temp, bn.temp_bytes, keys, keys_sorted, vals, vals_sorted, bn.L, 0, bn.bits, st,
+                                     true, w.unit_len, w.n_dev, w.hint, w.bounds),
+                 std::string(w.what.sort_why) + radix_sort_last_error() + ")");
+    }
+    RR_STAGE_CHECK(w.what.sort);
+    return stage(f, st, RR_STAGE_RANGES, w.what.expand, [&] {
+        launch_sortexpand<K>(keys_sorted, vals_sorted, gm.depth_keys, gm.ft, d.gx, d.gy, w.out_base, bn.point_list,
+                             w.ranges, w.open_bits, w.bounds, st);
+    });
 }
 
 // Tile lists for one frame: duplicate -> pairs into their bins -> per-bin depth order + tile lists
@@ -605,8 +475,6 @@ int render_tiles(const rr_frame* f, const Geom& gm, const Img& im, const Bin& bn
                  int H, int cull, bool early, BlendFwdArgs b, hipStream_t st) {
     const int gx = grid_x(W), gy = grid_y(H);
     const uint32_t L = bn.L;
-    K* keys = static_cast<K*>(bn.keys);
-    K* keys_sorted = static_cast<K*>(bn.keys_sorted);
     DupArgs<K> d{};
     d.P = P; d.splats = gm.splats; d.radii = radii;
     d.gx = gx; d.gy = gy; d.cull = cull;
@@ -615,117 +483,110 @@ int render_tiles(const rr_frame* f, const Geom& gm, const Img& im, const Bin& bn
     const bool gather = early && b_gather(W, H);
     const RadixPlan pa = tile_plan<K>(bn.temp, L, bn.bits, h.a);  // phase A (or the only phase)
     const RadixPlan pb = tile_plan<K>(bn.temp, L, bn.bits, h.b);  // phase B (windowed path)
-    bool starts_b = false;  // phase B's window starts computed with phase A's
     // window starts marked by the split scan (units of kSplitWin pairs), else a window-starts launch
     const bool marks_a = pa.unit_items == kSplitWin && (uint32_t)pa.units <= gm.lists.nwin;
     const bool marks_b = pb.unit_items == kSplitWin && (uint32_t)pb.units <= gm.lists.nwin;
     // phase A (or the only phase): its pairs for every tile
-    {
-        StageTimer tm(RR_STAGE_DUPLICATE, st);
-        d.n_list = &gm.ft->GA; d.idx = gm.lists.idx_a; d.off = gm.lists.off_a;
-        d.first = marks_a ? gm.lists.first_a : bn.first;
-        d.pair0 = 0; d.win = (uint32_t)pa.unit_items; d.nwin = pa.units; d.L_dev = &gm.ft->LA;
-        d.keys = keys; d.vals = bn.vals; d.dbits = pa.dbits0; d.counts = pa.counts;
-        d.starts_done = marks_a;
-        if (early && !gather && !marks_a && !marks_b) {
-            d.first_b = bn.first + pa.units; d.pair0_b = 0; d.win_b = (uint32_t)pb.unit_items; d.nwin_b = pb.units;
-            d.n_list_b = &gm.ft->GB; d.off_b = gm.lists.off_b;
-        }
-        starts_b = launch_duplicate<K>(d, st);
-        d.first_b = nullptr; d.nwin_b = 0; d.starts_done = false;
+    if (early && !gather && !marks_a && !marks_b) {  // phase B's window starts computed with phase A's
+        d.first_b = bn.first + pa.units; d.pair0_b = 0; d.win_b = (uint32_t)pb.unit_items; d.nwin_b = pb.units;
+        d.n_list_b = &gm.ft->GB; d.off_b = gm.lists.off_b;
     }
-    RR_STAGE_CHECK("duplicate");
-    {
-        StageTimer tm(RR_STAGE_TILE_SORT, st);
-        RR_CHECK(radix_sort_pairs<K>(bn.temp, bn.temp_bytes, keys, keys_sorted, bn.vals, bn.vals_sorted, L, 0, bn.bits,
-                                     st, true, nullptr, &gm.ft->LA, h.a, im.bounds_a),
-                 std::string("bin sort (") + radix_sort_last_error() + ")");
-    }
-    RR_STAGE_CHECK("bin sort");
-    {
-        StageTimer tm(RR_STAGE_RANGES, st);
-        launch_sortexpand<K>(keys_sorted, bn.vals_sorted, gm.depth_keys, gm.ft, gx, gy, 0u, bn.point_list, im.ranges,
-                             nullptr, im.bounds_a, st);
-    }
-    RR_STAGE_CHECK("sort-expand");
-    {
-        StageTimer tm(RR_STAGE_BLEND_FWD, st);
-        b.phase = early ? kBlendPhaseA : kBlendSingle;
-        // the registered backward workspace (render_frame), cleared in this launch's drain
-        if (b.clear) g_render_facts.clean = WsRange{b.clear, b.clear_n4 * sizeof(float4)};
-        launch_blend_fwd(b, st);
-        b.clear = nullptr;
-        b.clear_n4 = 0;
-    }
-    RR_STAGE_CHECK("blend forward");
+    bool starts_b = false, starts = false;
+    const WindowedPhase wa{0u, &gm.ft->GA, gm.lists.idx_a, gm.lists.off_a, marks_a ? gm.lists.first_a : bn.first,
+                           marks_a, &gm.ft->LA, pa, h.a, nullptr, &gm.ft->LA, im.bounds_a, 0u, im.ranges, nullptr,
+                           kLabelsA};
+    if (int rc = windowed_phase<K>(f, gm, bn, d, wa, st, &starts_b)) return rc;
+    b.phase = early ? kBlendPhaseA : kBlendSingle;
+    // (clears the registered backward workspace, render_frame, in its drain)
+    if (int rc = stage(f, st, RR_STAGE_BLEND_FWD, "blend forward", [&] { launch_blend_fwd(b, st); })) return rc;
+    b.clear = nullptr;
+    b.clear_n4 = 0;
     if (!early) return RR_OK;
     // phase B: its pairs, only for tiles phase A left open; region [L, 2L) of the pair arrays.  The
     // backward's tile order is computed on phase A's tile_max by an extra workgroup of the phase-B
     // duplicate launch (counters[1] = T marks it done)
     d.open_bits = im.open_bits; d.n_total = im.counters;
     d.order_cost = im.tile_max; d.order_out = im.order; d.order_flag = im.counters + 1; d.order_T = gx * gy;
+    if (P > 0) g_hand.facts.order = im.order;
     if (gather) {
-        {
-            StageTimer tm(RR_STAGE_DUPLICATE, st);
-            d.keys = keys + L; d.vals = bn.vals + L;
-            d.n_list = &gm.ft->GB; d.idx = gm.lists.idx_b;
-            d.gather_mark = im.counters + 2;
-            if (P > 0) g_render_facts.order = im.order;
-            launch_dup_gather<K>(d, st);
-        }
-        RR_STAGE_CHECK("duplicate (phase B gather)");
-        {
-            StageTimer tm(RR_STAGE_RANGES, st);
-            // phase B's tile lists right after phase A's
-            launch_sortexpand_small<K>(P, keys + L, bn.vals + L, im.counters, im.bin_cnt, bn.vals_sorted + L,
-                                       gm.depth_keys, gm.ft, gx, gy, 4u * L, bn.point_list, im.ranges_b, im.open_bits,
-                                       im.bounds_b, im.counters + 3, st);
-        }
-        RR_STAGE_CHECK("sort-expand (phase B gather)");
+        K* keys = static_cast<K*>(bn.keys);
+        d.keys = keys + L; d.vals = bn.vals + L;
+        d.n_list = &gm.ft->GB; d.idx = gm.lists.idx_b;
+        d.gather_mark = im.counters + 2;
+        if (int rc = stage(f, st, RR_STAGE_DUPLICATE, "duplicate (phase B gather)", [&] { launch_dup_gather<K>(d, st); }))
+            return rc;
+        // phase B's tile lists right after phase A's
+        if (int rc = stage(f, st, RR_STAGE_RANGES, "sort-expand (phase B gather)", [&] {
+                launch_sortexpand_small<K>(P, keys + L, bn.vals + L, im.counters, im.bin_cnt, bn.vals_sorted + L,
+                                           gm.depth_keys, gm.ft, gx, gy, 4u * L, bn.point_list, im.ranges_b,
+                                           im.open_bits, im.bounds_b, im.counters + 3, st);
+            }))
+            return rc;
     } else {
-        {
-            StageTimer tm(RR_STAGE_DUPLICATE, st);
-            d.n_list = &gm.ft->GB; d.idx = gm.lists.idx_b; d.off = gm.lists.off_b;
-            d.first = marks_b ? gm.lists.first_b : bn.first + pa.units;
-            d.pair0 = 0; d.win = (uint32_t)pb.unit_items; d.nwin = pb.units;
-            d.L_dev = &gm.ft->LB;
-            d.keys = keys + L; d.vals = bn.vals + L; d.dbits = pb.dbits0; d.counts = pb.counts;
-            d.unit_len = bn.unit_len;
-            d.zero = nullptr; d.nzero = 0;
-            d.starts_done = starts_b || marks_b;
-            if (P > 0) g_render_facts.order = im.order;
-            launch_duplicate<K>(d, st);
-        }
-        RR_STAGE_CHECK("duplicate (phase B)");
-        {
-            StageTimer tm(RR_STAGE_TILE_SORT, st);
-            RR_CHECK(radix_sort_pairs<K>(bn.temp, bn.temp_bytes, keys + L, keys_sorted + L, bn.vals + L,
-                                         bn.vals_sorted + L, L, 0, bn.bits, st, true, bn.unit_len, im.counters, h.b,
-                                         im.bounds_b),
-                     std::string("bin sort, phase B (") + radix_sort_last_error() + ")");
-        }
-        RR_STAGE_CHECK("bin sort (phase B)");
-        {
-            StageTimer tm(RR_STAGE_RANGES, st);
-            launch_sortexpand<K>(keys_sorted + L, bn.vals_sorted + L, gm.depth_keys, gm.ft, gx, gy, 4u * L,
-                                 bn.point_list, im.ranges_b, im.open_bits, im.bounds_b, st);
-        }
-        RR_STAGE_CHECK("sort-expand (phase B)");
+        const WindowedPhase wb{L, &gm.ft->GB, gm.lists.idx_b, gm.lists.off_b,
+                               marks_b ? gm.lists.first_b : bn.first + pa.units, starts_b || marks_b, &gm.ft->LB, pb,
+                               h.b, bn.unit_len, im.counters, im.bounds_b, 4u * L, im.ranges_b, im.open_bits,
+                               kLabelsB};
+        if (int rc = windowed_phase<K>(f, gm, bn, d, wb, st, &starts)) return rc;
     }
-    {
-        StageTimer tm(RR_STAGE_BLEND_FWD, st);
-        b.phase = kBlendPhaseB;
-        launch_blend_fwd(b, st);
-    }
-    RR_STAGE_CHECK("blend forward (phase B)");
-    return RR_OK;
+    b.phase = kBlendPhaseB;
+    return stage(f, st, RR_STAGE_BLEND_FWD, "blend forward (phase B)", [&] { launch_blend_fwd(b, st); });
 }
 
+// Binning + blend of a frame whose pairs were just counted (count_pairs) into this image buffer.
 int render_frame(const rr_frame* f, const rr_camera* cam, const int* radii, void* geom_buffer, void* image_buffer,
                  void* binning_buffer, size_t binning_bytes, int num_pairs, float* out_color, float* out_depth,
-                 float* out_normal, void* stream);int render_frame(const rr_frame* f, const rr_camera* cam, const int* radii, void* geom_buffer, void* image_buffer,
-                 void* binning_buffer, size_t binning_bytes, int num_pairs, float* out_color, float* out_depth,
-                 float* out_normal, void* stream);
+                 float* out_normal, void* stream) {
+    const int P = f->P, W = f->width, H = f->height, L = num_pairs;
+    const int cull = (f->flags & RR_FLAG_NO_TILE_CULLING) ? 0 : 1;
+    const WsRange reg = std::exchange(g_hand.fwd_ws, WsRange{});  // used by this render, or dropped by it
+    if (P == 0) return RR_OK;
+    if (!out_color || !out_depth || !geom_buffer || !image_buffer || (L > 0 && !binning_buffer))
+        return fail(RR_ERR_ARG, "null buffer");
+    const Geom gm = carve_geom(geom_buffer, P);
+    const Img im = carve_img(image_buffer, W, H);
+    if (!g_hand.begin_render(im.final_T, reg))
+        return fail(RR_ERR_ARG, "render without a pair count of this image buffer (one render per rr_forward_geometry / "
+                                "rr_forward_from_geometry on this thread)");
+    const Bin bn = carve_bin(binning_buffer, L, W, H);
+    if (L > 0 && binning_bytes < bn.total) return fail(RR_ERR_CAPACITY, "binning buffer too small");
+    hipStream_t st = (hipStream_t)stream;
+    const int gx = grid_x(W), gy = grid_y(H);
+    // (the per-frame block of the image buffer was cleared by count_pairs' split scan)
+    BlendFwdArgs b{};
+    b.W = W; b.H = H; b.gx = gx; b.gy = gy;
+    b.ranges = im.ranges; b.ranges_b = im.ranges_b; b.open = im.open; b.open_bits = im.open_bits;
+    b.point_list = bn.point_list; b.splats = gm.splats; b.bg = cam->background;
+    b.final_T = im.final_T; b.n_contrib = im.n_contrib; b.tile_max = im.tile_max;
+    b.clear = static_cast<float4*>(reg.ptr);
+    b.clear_n4 = reg.bytes / sizeof(float4);
+    b.out_color = out_color; b.out_depth = out_depth;
+    b.normals = out_normal ? gm.normals : nullptr; b.out_normal = out_normal;
+    if (L == 0) {  // no pairs: every tile keeps the background (one blend over empty lists)
+        b.phase = kBlendSingle;
+        return g_hand.end_render(stage(f, st, RR_STAGE_BLEND_FWD, "blend forward", [&] { launch_blend_fwd(b, st); }));
+    }
+    // the split the depth cut makes (its one-phase conditions but "no sampled pair", which leaves
+    // phase B empty on the device)
+    const Tuning& tu = tuning();
+    const bool early = !(f->flags & RR_FLAG_FULL_BINNING) && tu.early_den > 1 && (uint32_t)L >= tu.early_min;
+    return g_hand.end_render(bn.wide ? render_tiles<uint32_t>(f, gm, im, bn, radii, P, W, H, cull, early, b, st)
+                                     : render_tiles<uint16_t>(f, gm, im, bn, radii, P, W, H, cull, early, b, st));
+}
+
+// The tail of rr_forward and rr_forward_from_geometry after the pair count: the binning buffer's
+// size query, RR_INCOMPLETE when the given one is smaller, else the render.
+int finish_forward(const rr_frame* f, const rr_camera* cam, const int* radii, void* geom_buffer, void* image_buffer,
+                   void* binning_buffer, size_t binning_bytes, int num_pairs, size_t* binning_needed, float* out_color,
+                   float* out_depth, void* stream) {
+    const size_t need = num_pairs > 0 ? carve_bin(nullptr, num_pairs, f->width, f->height).total : 0;
+    *binning_needed = need;
+    if (binning_bytes < need) return RR_INCOMPLETE;
+    // (rr_forward only: rr_forward_from_geometry refuses the flag before it counts)
+    if (f->flags & RR_FLAG_AUX_NORMAL) return fail(RR_ERR_ARG, "RR_FLAG_AUX_NORMAL: use rr_forward_render_aux");
+    return render_frame(f, cam, radii, geom_buffer, image_buffer, binning_buffer, binning_bytes, num_pairs, out_color,
+                        out_depth, nullptr, stream);
+}
 
 // Accumulator clear (+ the backward's tile order) and the blend backward: gacc [P][GACC_STRIDE]
 // receives every Gaussian's dmean2D / dconic / dopacity / dcolor sums of the frame.
@@ -735,14 +596,15 @@ int blend_backward(const rr_frame* f, const rr_camera* cam, const void* geom_buf
     const Geom gm = carve_geom(const_cast<void*>(geom_buffer), P);
     const Img im = carve_img(const_cast<void*>(image_buffer), W, H);
     // point_list sits at the start of the binning buffer, so its position does not depend on the
-    // pair count; tiles whose forward blended nothing (tile_max 0) never read it
+    // pair count (tests/host/layout_check.hip); tiles whose forward blended nothing (tile_max 0)
+    // never read it
     const Bin bn = carve_bin(const_cast<void*>(binning_buffer), 0, W, H);
     const int gx = grid_x(W), gy = grid_y(H);
     const bool blend = L > 0 && binning_buffer;
     uint32_t* order = blend ? im.order : nullptr;  // heaviest tiles first
     // the accumulators already zero-filled by the forward (rr_set_forward_workspace): no clear
     const size_t nacc = (size_t)P * GACC_STRIDE;
-    const FrameFacts facts = take_facts(im.final_T);  // this backward's accumulation dirties the workspace
+    const FrameFacts facts = Handoff::take_facts(im.final_T);  // this backward's accumulation dirties the workspace
     const bool clean = (f->flags & RR_FLAG_WORKSPACE_REGISTERED) && facts.clean.ptr == gacc &&
                        facts.clean.bytes >= nacc * sizeof(float);
     const bool order_ready = order && facts.order == order;
@@ -771,12 +633,35 @@ int blend_backward(const rr_frame* f, const rr_camera* cam, const void* geom_buf
 
 extern "C" {
 
-int rr_forward_render(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
-                      void* geom_buffer, void* image_buffer, void* binning_buffer, size_t binning_bytes,
-                      int num_pairs, float* out_color, float* out_depth, void* stream) {
-    if (f && (f->flags & RR_FLAG_AUX_NORMAL)) return fail(RR_ERR_ARG, "RR_FLAG_AUX_NORMAL: use rr_forward_render_aux");
-    return rr_forward_render_aux(f, cam, g, radii, geom_buffer, image_buffer, binning_buffer, binning_bytes, num_pairs,
-                                 out_color, out_depth, nullptr, stream);
+size_t rr_geometry_bytes(int P) { return carve_geom(nullptr, P).total; }
+size_t rr_image_bytes(int width, int height) { return carve_img(nullptr, width, height).total; }
+size_t rr_binning_bytes(int num_rendered, int width, int height) {
+    return carve_bin(nullptr, num_rendered, width, height).total;
+}
+size_t rr_backward_workspace_bytes(int P) { return align_up((size_t)std::max(P, 1) * GACC_STRIDE * sizeof(float)); }
+
+int rr_forward_geometry(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, int* radii, void* geom_buffer,
+                        size_t geom_bytes, void* image_buffer, size_t image_bytes, int* num_rendered,
+                        int* num_pairs, void* stream) {
+    int rc = validate(f, cam, g, true);
+    if (rc) return rc;
+    if (!num_rendered || !num_pairs) return fail(RR_ERR_ARG, "num_rendered / num_pairs is null");
+    *num_rendered = 0;
+    *num_pairs = 0;
+    const int P = f->P, W = f->width, H = f->height;
+    if (P == 0) return RR_OK;
+    if (!radii || !geom_buffer || !image_buffer) return fail(RR_ERR_ARG, "null output buffer");
+    const Geom gm = carve_geom(geom_buffer, P);
+    const Img im = carve_img(image_buffer, W, H);
+    if (geom_bytes < gm.total || image_bytes < im.total) return fail(RR_ERR_CAPACITY, "scratch buffer too small");
+    hipStream_t st = (hipStream_t)stream;
+    PreArgs a = pre_args(f, cam, g);
+    a.radii = radii; a.splats = gm.splats; a.tiles = gm.tiles; a.depth_keys = gm.depth_keys;
+    a.normals = (f->flags & RR_FLAG_AUX_NORMAL) ? gm.normals : nullptr;
+    a.block_sums = gm.block_sums;
+    a.block_wide = gm.block_wide;
+    if (int rc2 = stage(f, st, RR_STAGE_PREPROCESS, "preprocess", [&] { launch_preprocess(a, st); })) return rc2;
+    return count_pairs(f, gm, im, P, st, num_rendered, num_pairs);
 }
 
 int rr_forward_render_aux(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
@@ -790,66 +675,13 @@ int rr_forward_render_aux(const rr_frame* f, const rr_camera* cam, const rr_gaus
                         out_depth, out_normal, stream);
 }
 
-}  // extern "C"
-
-namespace {
-
-// Binning + blend of a frame whose pairs were just counted (count_pairs) into this image buffer.
-int render_frame(const rr_frame* f, const rr_camera* cam, const int* radii, void* geom_buffer, void* image_buffer,
-                 void* binning_buffer, size_t binning_bytes, int num_pairs, float* out_color, float* out_depth,
-                 float* out_normal, void* stream) {
-    const int P = f->P, W = f->width, H = f->height, L = num_pairs;
-    const int cull = (f->flags & RR_FLAG_NO_TILE_CULLING) ? 0 : 1;
-    // a workspace registration is used by this render (or dropped by it) either way
-    const WsRange reg = g_fwd_ws;
-    g_fwd_ws = WsRange{};
-    if (P == 0) return RR_OK;
-    if (!out_color || !out_depth || !geom_buffer || !image_buffer || (L > 0 && !binning_buffer))
-        return fail(RR_ERR_ARG, "null buffer");
-    const Geom gm = carve_geom(geom_buffer, P);
-    const Img im = carve_img(image_buffer, W, H);
-    if (g_counted_img != im.final_T)
-        return fail(RR_ERR_ARG, "render without a pair count of this image buffer (one render per rr_forward_geometry / "
-                                "rr_forward_from_geometry on this thread)");
-    g_counted_img = nullptr;
-    g_render_facts = FrameFacts{im.final_T, WsRange{}, nullptr};
-    publish_facts(g_render_facts);  // drops an earlier render's facts of this buffer
-    const Bin bn = carve_bin(binning_buffer, L, W, H);
-    if (L > 0 && binning_bytes < bn.total) return fail(RR_ERR_CAPACITY, "binning buffer too small");
-    hipStream_t st = (hipStream_t)stream;
-    const int gx = grid_x(W), gy = grid_y(H);
-    // (the per-frame block of the image buffer was cleared by count_pairs' split scan)
-    BlendFwdArgs b{};
-    b.W = W; b.H = H; b.gx = gx; b.gy = gy;
-    b.ranges = im.ranges; b.ranges_b = im.ranges_b; b.open = im.open; b.open_bits = im.open_bits;
-    b.point_list = bn.point_list; b.splats = gm.splats; b.bg = cam->background;
-    b.final_T = im.final_T; b.n_contrib = im.n_contrib; b.tile_max = im.tile_max;
-    b.clear = static_cast<float4*>(reg.ptr);
-    b.clear_n4 = reg.bytes / sizeof(float4);
-    b.out_color = out_color; b.out_depth = out_depth;
-    b.normals = out_normal ? gm.normals : nullptr; b.out_normal = out_normal;
-    if (L == 0) {  // no pairs: every tile keeps the background (one blend over empty lists)
-        StageTimer tm(RR_STAGE_BLEND_FWD, st);
-        b.phase = kBlendSingle;
-        launch_blend_fwd(b, st);
-        if (b.clear) g_render_facts.clean = WsRange{b.clear, b.clear_n4 * sizeof(float4)};
-        const int rc = check(f, st, "blend forward");
-        if (rc == RR_OK) publish_facts(g_render_facts);
-        return rc;
-    }
-    // the split the depth cut makes (its one-phase conditions but "no sampled pair", which leaves
-    // phase B empty on the device)
-    const Tuning& tu = tuning();
-    const bool early = !(f->flags & RR_FLAG_FULL_BINNING) && tu.early_den > 1 && (uint32_t)L >= tu.early_min;
-    const int rc = bn.wide ? render_tiles<uint32_t>(f, gm, im, bn, radii, P, W, H, cull, early, b, st)
-                           : render_tiles<uint16_t>(f, gm, im, bn, radii, P, W, H, cull, early, b, st);
-    if (rc == RR_OK) publish_facts(g_render_facts);
-    return rc;
+int rr_forward_render(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
+                      void* geom_buffer, void* image_buffer, void* binning_buffer, size_t binning_bytes,
+                      int num_pairs, float* out_color, float* out_depth, void* stream) {
+    if (f && (f->flags & RR_FLAG_AUX_NORMAL)) return fail(RR_ERR_ARG, "RR_FLAG_AUX_NORMAL: use rr_forward_render_aux");
+    return rr_forward_render_aux(f, cam, g, radii, geom_buffer, image_buffer, binning_buffer, binning_bytes, num_pairs,
+                                 out_color, out_depth, nullptr, stream);
 }
-
-}  // namespace
-
-extern "C" {
 
 int rr_forward(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, int* radii, void* geom_buffer,
                size_t geom_bytes, void* image_buffer, size_t image_bytes, void* binning_buffer, size_t binning_bytes,
@@ -860,11 +692,8 @@ int rr_forward(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, i
     int rc = rr_forward_geometry(f, cam, g, radii, geom_buffer, geom_bytes, image_buffer, image_bytes, num_rendered,
                                  num_pairs, stream);
     if (rc != RR_OK || f->P == 0) return rc;
-    const size_t need = *num_pairs > 0 ? carve_bin(nullptr, *num_pairs, f->width, f->height).total : 0;
-    *binning_needed = need;
-    if (binning_bytes < need) return RR_INCOMPLETE;
-    return rr_forward_render(f, cam, g, radii, geom_buffer, image_buffer, binning_buffer, binning_bytes, *num_pairs,
-                             out_color, out_depth, stream);
+    return finish_forward(f, cam, radii, geom_buffer, image_buffer, binning_buffer, binning_bytes, *num_pairs,
+                          binning_needed, out_color, out_depth, stream);
 }
 
 int rr_backward(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
@@ -879,15 +708,8 @@ int rr_backward(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, 
     const bool raw = (f->flags & RR_FLAG_RAW_PARAMS) != 0;
     const rr_adam* ad = out->adam;
     if (ad && !raw) return fail(RR_ERR_ARG, "the fused optimizer step needs raw-parameter mode");
-    if (ad) {
-        const rr_adam_group* gs[6] = {&ad->xyz, &ad->f_dc, &ad->f_rest, &ad->opacity, &ad->scaling, &ad->rotation};
-        const void* in[6] = {g->means3D, g->shs, g->shs_rest, g->opacities, g->scales, g->rotations};
-        for (int i = 0; i < 6; i++) {
-            if (i == 2 && f->M <= 1) continue;
-            if (!gs[i]->param || !gs[i]->exp_avg || !gs[i]->exp_avg_sq)
-                return fail(RR_ERR_ARG, "null Adam group array");
-            if (gs[i]->param != in[i]) return fail(RR_ERR_ARG, "Adam group param must be the matching input array");
-        }
+    if (ad) {  // every group is stepped (which rr_grads.next relies on)
+        if (int rc2 = check_adam(f, g, ad, true)) return rc2;
     } else if (!out->dL_dopacity || !out->dL_dmeans3D || !out->dL_dscales || !out->dL_drotations ||
                (f->M > 0 && !out->dL_dsh) ||
                (!raw && (!out->dL_dmeans2D || !out->dL_dcolors || !out->dL_dcov3D)) ||
@@ -913,33 +735,23 @@ int rr_backward(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, 
             return fail(RR_ERR_ARG, "rr_next_frame: camera arrays are required");
         if (nx->geom_bytes < carve_geom(nullptr, P).total) return fail(RR_ERR_CAPACITY, "next geometry buffer too small");
         if (nx->geom_buffer == geom_buffer) return fail(RR_ERR_ARG, "rr_next_frame: the next frame needs its own geometry buffer");
-        const rr_adam_group* gs[6] = {&ad->xyz, &ad->f_dc, &ad->f_rest, &ad->opacity, &ad->scaling, &ad->rotation};
-        for (int i = 0; i < 6; i++)
-            if (!gs[i]->param && !(i == 2 && f->M <= 1))
-                return fail(RR_ERR_ARG, "rr_next_frame: every Adam group must be stepped");
     }
     hipStream_t st = (hipStream_t)stream;
     float* gacc = static_cast<float*>(workspace);
     if (int rc2 = blend_backward(f, cam, geom_buffer, image_buffer, binning_buffer, L, dL_dpix, gacc, st)) return rc2;
     {
         StageTimer tm(RR_STAGE_GAUSS_BWD, st);
-        GaussBwdArgs a{};
-        a.P = P; a.D = f->D; a.M = f->M;
+        GaussBwdArgs a = gauss_bwd_args(f, g, out);
         a.tanfovx = f->tan_fovx; a.tanfovy = f->tan_fovy;
-        a.focal_y = H / (2.0f * f->tan_fovy);
-        a.focal_x = W / (2.0f * f->tan_fovx);
-        a.scale_modifier = f->scale_modifier; a.low_pass = f->low_pass;
-        a.means3D = g->means3D; a.shs = g->shs; a.scales = g->scales; a.rotations = g->rotations;
+        a.focal_y = focal(H, f->tan_fovy);
+        a.focal_x = focal(W, f->tan_fovx);
+        a.low_pass = f->low_pass;
         a.cov3D_precomp = g->cov3D_precomp; a.view = cam->viewmatrix; a.proj = cam->projmatrix;
         a.campos = cam->campos; a.radii = radii; a.gacc = gacc;
         a.dL_dmeans2D = out->dL_dmeans2D; a.dL_dcolors = out->dL_dcolors; a.dL_dopacity = out->dL_dopacity;
         a.dL_dmeans3D = out->dL_dmeans3D; a.dL_dcov3D = out->dL_dcov3D; a.dL_dsh = f->M > 0 ? out->dL_dsh : nullptr;
         a.dL_dscales = out->dL_dscales; a.dL_drot = out->dL_drotations;
-        a.raw = raw ? 1 : 0; a.opacities = g->opacities; a.shs_rest = g->shs_rest;
         a.dL_dsh_rest = out->dL_dsh_rest;
-        a.grad_accum = out->grad_accum; a.denom = out->denom; a.max_radii2D = out->max_radii2D;
-        a.use_adam = ad ? 1 : 0;
-        if (ad) a.adam = *ad;  // by value: the kernel must not dereference host memory
         if (nx) {
             const Geom ng = carve_geom(nx->geom_buffer, P);
             PreArgs n = pre_args(nx->frame, nx->cam, g);
@@ -951,6 +763,31 @@ int rr_backward(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, 
         launch_gauss_bwd(a, st);
     }
     RR_STAGE_CHECK("gaussian backward");
+    return RR_OK;
+}
+
+int rr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix, uint8_t* present,
+                    void* stream) {
+    (void)projmatrix;
+    if (P < 0) return fail(RR_ERR_ARG, "bad P");
+    if (P == 0) return RR_OK;
+    if (!means3D || !viewmatrix || !present) return fail(RR_ERR_ARG, "null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    launch_mark_visible(P, means3D, viewmatrix, present, st);
+    return check(nullptr, st, "mark_visible");
+}
+
+int rr_set_forward_workspace(void* workspace, size_t bytes) {
+    if (workspace && (((uintptr_t)workspace & 15u) != 0 || bytes % 16 != 0))
+        return fail(RR_ERR_ARG, "workspace must be 16-byte aligned and a multiple of 16 bytes");
+    g_hand.fwd_ws = workspace && bytes ? WsRange{workspace, bytes} : WsRange{};
+    return RR_OK;
+}
+
+int rr_host_wait_stats(int reset, int64_t* wait_ns, int64_t* waits) {
+    if (wait_ns) *wait_ns = g_wait_ns;
+    if (waits) *waits = g_waits;
+    if (reset) g_wait_ns = g_waits = 0;
     return RR_OK;
 }
 
@@ -988,12 +825,7 @@ int rr_preprocess_rows(const rr_frame* f, const rr_camera* cam, const rr_gaussia
     a.block_sums = static_cast<uint2*>(block_sums);
     a.block_wide = static_cast<uint32_t*>(block_wide);
     a.n_out = n_rows;
-    {
-        StageTimer tm(RR_STAGE_PREPROCESS, st);
-        launch_preprocess(a, st);
-    }
-    RR_STAGE_CHECK("preprocess (rows)");
-    return RR_OK;
+    return stage(f, st, RR_STAGE_PREPROCESS, "preprocess (rows)", [&] { launch_preprocess(a, st); });
 }
 
 int rr_preprocess_rows_views(const rr_frame* f, const rr_view* views, int num_views, const rr_gaussians* g,
@@ -1003,15 +835,12 @@ int rr_preprocess_rows_views(const rr_frame* f, const rr_view* views, int num_vi
     if (num_views < 1 || num_views > RR_MAX_VIEWS) return fail(RR_ERR_ARG, "1 <= num_views <= RR_MAX_VIEWS");
     if (n_rows < f->P || (n_rows % 256) != 0) return fail(RR_ERR_ARG, "n_rows must be >= P and a multiple of 256");
     if (f->flags & RR_FLAG_AUX_NORMAL) return fail(RR_ERR_ARG, "row blocks carry no aux normals");
-    for (int v = 0; v < num_views; v++) {
-        const rr_view& w = views[v];
-        if (!w.viewmatrix || !w.projmatrix || !w.campos || w.width <= 0 || w.height <= 0)
-            return fail(RR_ERR_ARG, "bad view");
-    }
+    int rc = check_views(views, num_views);
+    if (rc) return rc;
     // the frame's own validation, with view 0 standing in for the camera (the preprocess reads no
     // background)
     const rr_camera cam0{views[0].viewmatrix, views[0].viewmatrix, views[0].projmatrix, views[0].campos};
-    int rc = validate(f, &cam0, g, true);
+    rc = validate(f, &cam0, g, true);
     if (rc) return rc;
     if (n_rows == 0) return RR_OK;
     if (!out) return fail(RR_ERR_ARG, "null output buffer");
@@ -1034,27 +863,12 @@ int rr_preprocess_rows_views(const rr_frame* f, const rr_view* views, int num_vi
     vs.stride = view_stride;
     for (int v = 0; v < num_views; v++) {
         const rr_view& w = views[v];
-        PreView& c = vs.v[v];
-        c.view = w.viewmatrix;
-        c.proj = w.projmatrix;
-        c.campos = w.campos;
-        c.tanfovx = w.tan_fovx;
-        c.tanfovy = w.tan_fovy;
-        c.focal_x = w.width / (2.0f * w.tan_fovx);
-        c.focal_y = w.height / (2.0f * w.tan_fovy);
-        c.low_pass = w.low_pass;
-        c.W = w.width;
-        c.H = w.height;
-        c.gx = grid_x(w.width);
-        c.gy = grid_y(w.height);
+        vs.v[v] = PreView{w.viewmatrix, w.projmatrix, w.campos, w.tan_fovx, w.tan_fovy,
+                          focal(w.width, w.tan_fovx), focal(w.height, w.tan_fovy), w.low_pass,
+                          w.width, w.height, grid_x(w.width), grid_y(w.height)};
     }
     hipStream_t st = (hipStream_t)stream;
-    {
-        StageTimer tm(RR_STAGE_PREPROCESS, st);
-        launch_preprocess_views(a, vs, st);
-    }
-    RR_STAGE_CHECK("preprocess (rows, views)");
-    return RR_OK;
+    return stage(f, st, RR_STAGE_PREPROCESS, "preprocess (rows, views)", [&] { launch_preprocess_views(a, vs, st); });
 }
 
 int rr_unpack_rows(int world, int rows_per_rank, const void* recv, size_t chunk_bytes, const size_t field_offsets[5],
@@ -1092,13 +906,9 @@ int rr_forward_from_geometry(const rr_frame* f, const rr_camera* cam, const int*
     const Geom gm = carve_geom(geom_buffer, P);
     const Img im = carve_img(image_buffer, W, H);
     if (geom_bytes < gm.total || image_bytes < im.total) return fail(RR_ERR_CAPACITY, "scratch buffer too small");
-    hipStream_t st = (hipStream_t)stream;
-    if (int rc = count_pairs(f, gm, im, P, st, num_rendered, num_pairs)) return rc;
-    const size_t need = *num_pairs > 0 ? carve_bin(nullptr, *num_pairs, W, H).total : 0;
-    *binning_needed = need;
-    if (binning_bytes < need) return RR_INCOMPLETE;
-    return render_frame(f, cam, radii, geom_buffer, image_buffer, binning_buffer, binning_bytes, *num_pairs, out_color,
-                        out_depth, nullptr, stream);
+    if (int rc = count_pairs(f, gm, im, P, (hipStream_t)stream, num_rendered, num_pairs)) return rc;
+    return finish_forward(f, cam, radii, geom_buffer, image_buffer, binning_buffer, binning_bytes, *num_pairs,
+                          binning_needed, out_color, out_depth, stream);
 }
 
 int rr_forward_render_geometry(const rr_frame* f, const rr_camera* cam, const int* radii, void* geom_buffer,
@@ -1151,33 +961,17 @@ int rr_gauss_backward_views(const rr_frame* f, const rr_view* views, int num_vie
         return fail(RR_ERR_ARG, "the sharded backward writes no gradient arrays (Adam and statistics only)");
     if (out->grad_accum && (!out->denom || !out->max_radii2D))
         return fail(RR_ERR_ARG, "densification statistics need grad_accum, denom, max_radii2D");
-    const rr_adam* ad = out->adam;
-    if (ad) {
-        const rr_adam_group* gs[6] = {&ad->xyz, &ad->f_dc, &ad->f_rest, &ad->opacity, &ad->scaling, &ad->rotation};
-        const void* in[6] = {g->means3D, g->shs, g->shs_rest, g->opacities, g->scales, g->rotations};
-        for (int i = 0; i < 6; i++) {
-            if (!gs[i]->param || (i == 2 && f->M <= 1)) continue;  // a group without param is not stepped
-            if (!gs[i]->exp_avg || !gs[i]->exp_avg_sq) return fail(RR_ERR_ARG, "null Adam moment array");
-            if (gs[i]->param != in[i]) return fail(RR_ERR_ARG, "Adam group param must be the matching input array");
-        }
-    }
+    if (out->adam)  // a group without param is not stepped
+        if (int rc = check_adam(f, g, out->adam, false)) return rc;
+    if (int rc = check_views(views, num_views)) return rc;
     ViewCam cams[RR_MAX_VIEWS];
     for (int v = 0; v < num_views; v++) {
         const rr_view& w = views[v];
-        if (!w.viewmatrix || !w.projmatrix || !w.campos || w.width <= 0 || w.height <= 0)
-            return fail(RR_ERR_ARG, "bad view");
         cams[v] = ViewCam{w.viewmatrix, w.projmatrix, w.campos, w.tan_fovx, w.tan_fovy,
-                          w.width / (2.0f * w.tan_fovx), w.height / (2.0f * w.tan_fovy), w.low_pass};
+                          focal(w.width, w.tan_fovx), focal(w.height, w.tan_fovy), w.low_pass};
     }
     hipStream_t st = (hipStream_t)stream;
-    GaussBwdArgs a{};
-    a.P = P; a.D = f->D; a.M = f->M;
-    a.scale_modifier = f->scale_modifier;
-    a.means3D = g->means3D; a.shs = g->shs; a.scales = g->scales; a.rotations = g->rotations;
-    a.raw = 1; a.opacities = g->opacities; a.shs_rest = g->shs_rest;
-    a.grad_accum = out->grad_accum; a.denom = out->denom; a.max_radii2D = out->max_radii2D;
-    a.use_adam = ad ? 1 : 0;
-    if (ad) a.adam = *ad;
+    const GaussBwdArgs a = gauss_bwd_args(f, g, out);
     {
         StageTimer tm(RR_STAGE_GAUSS_BWD, st);
         if (launch_gauss_bwd_views(a, cams, num_views, records, record_rows, grad_scale, st))
@@ -1186,15 +980,38 @@ int rr_gauss_backward_views(const rr_frame* f, const rr_view* views, int num_vie
     return check(f, st, "gaussian backward (views)");
 }
 
-int rr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix, uint8_t* present,
-                    void* stream) {
-    (void)projmatrix;
-    if (P < 0) return fail(RR_ERR_ARG, "bad P");
-    if (P == 0) return RR_OK;
-    if (!means3D || !viewmatrix || !present) return fail(RR_ERR_ARG, "null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    launch_mark_visible(P, means3D, viewmatrix, present, st);
-    return check(nullptr, st, "mark_visible");
+// ---- tuning, statistics, debug views, the per-stage profile ----
+const char* rr_last_error(void) { return g_err.c_str(); }
+const char* rr_version(void) { return "rain_amd-raster 0.1 gfx950"; }
+
+int rr_set_tuning(const char* key, int value) {
+    if (!key) return fail(RR_ERR_ARG, "unknown tuning key: (null)");
+    const std::string k(key);
+    Tuning& tu = tuning();
+    const Tuning dflt{};
+    if (k == "early_den") tu.early_den = value > 0 ? (uint32_t)value : dflt.early_den;
+    else if (k == "pair_scan_direct_blocks") tu.pair_scan_direct_blocks = value >= 0 ? value : dflt.pair_scan_direct_blocks;
+    else if (k == "wide_bin_keys") tu.wide_bin_keys = value != 0;
+    else if (k == "phase_b_gather") tu.b_gather = value != 0;
+    else if (k == "dup_b_rows") tu.dup_b_rows = value != 0;
+    else if (k == "dup_big_bins") tu.dup_big_bins = value >= 0 ? value : dflt.dup_big_bins;
+    else if (k == "sx_bucket") tu.sx_bucket = value != 0;
+    else if (k == "sx_lds_cap") tu.sx_lds_cap = value > 0 ? value : 0;
+    else if (k == "sort_min_units") tu.sort_min_units = value > 0 ? value : dflt.sort_min_units;
+    else if (k == "sort_min_units_tile") tu.sort_min_units_tile = value > 0 ? value : dflt.sort_min_units_tile;
+    else if (k == "sort_max_rounds")
+        tu.sort_max_rounds = (value == 1 || value == 2 || value == 4 || value == 8) ? value : dflt.sort_max_rounds;
+    else return fail(RR_ERR_ARG, "unknown tuning key: " + k);
+    return RR_OK;
+}
+
+int rr_set_binning_config(int split_denominator, int min_pairs) {
+    if (split_denominator < 0 || min_pairs < 0) return fail(RR_ERR_ARG, "negative binning config");
+    Tuning& tu = tuning();
+    const Tuning dflt{};
+    tu.early_den = split_denominator == 0 ? dflt.early_den : (uint32_t)split_denominator;
+    tu.early_min = min_pairs == 0 ? dflt.early_min : (uint32_t)min_pairs;
+    return RR_OK;
 }
 
 int rr_read_frame_stats(const rr_frame* f, const void* geom_buffer, const void* image_buffer, rr_frame_stats* out,
@@ -1214,9 +1031,7 @@ int rr_read_frame_stats(const rr_frame* f, const void* geom_buffer, const void* 
     RR_CHECK(hipMemcpyAsync(&ft, gm.ft, sizeof(ft), hipMemcpyDeviceToHost, st), "stats");
     RR_CHECK(hipMemcpyAsync(per.data(), gm.tiles, (size_t)P * sizeof(uint2), hipMemcpyDeviceToHost, st), "stats");
     RR_CHECK(hipMemcpyAsync(tm.data(), im.tile_max, (size_t)T * 4, hipMemcpyDeviceToHost, st), "stats");
-    // [0] phase-B pairs (the gather path: slots reserved), [2] phase B took the gather path,
-    // [3] phase-B pairs the gather path's bin runs hold
-    uint32_t cnt[4] = {0u, 0u, 0u, 0u};
+    uint32_t cnt[4] = {0u, 0u, 0u, 0u};  // rr_layout.hpp Img::counters
     RR_CHECK(hipMemcpyAsync(cnt, im.counters, sizeof(cnt), hipMemcpyDeviceToHost, st), "stats");
     RR_CHECK(hipStreamSynchronize(st), "stats");
     int64_t vis = 0;
@@ -1255,43 +1070,6 @@ int rr_debug_set_fwd_trace(void* dev_buf) {
     return RR_OK;
 }
 
-int rr_set_forward_workspace(void* workspace, size_t bytes) {
-    if (workspace && (((uintptr_t)workspace & 15u) != 0 || bytes % 16 != 0))
-        return fail(RR_ERR_ARG, "workspace must be 16-byte aligned and a multiple of 16 bytes");
-    g_fwd_ws = workspace && bytes ? WsRange{workspace, bytes} : WsRange{};
-    return RR_OK;
-}
-
-int rr_set_tuning(const char* key, int value) {
-    if (!key) return fail(RR_ERR_ARG, "unknown tuning key: (null)");
-    const std::string k(key);
-    Tuning& tu = tuning();
-    const Tuning dflt{};
-    if (k == "early_den") tu.early_den = value > 0 ? (uint32_t)value : dflt.early_den;
-    else if (k == "pair_scan_direct_blocks") tu.pair_scan_direct_blocks = value >= 0 ? value : dflt.pair_scan_direct_blocks;
-    else if (k == "wide_bin_keys") tu.wide_bin_keys = value != 0;
-    else if (k == "phase_b_gather") tu.b_gather = value != 0;
-    else if (k == "dup_b_rows") tu.dup_b_rows = value != 0;
-    else if (k == "dup_big_bins") tu.dup_big_bins = value >= 0 ? value : dflt.dup_big_bins;
-    else if (k == "sx_bucket") tu.sx_bucket = value != 0;
-    else if (k == "sx_lds_cap") tu.sx_lds_cap = value > 0 ? value : 0;
-    else if (k == "sort_min_units") tu.sort_min_units = value > 0 ? value : dflt.sort_min_units;
-    else if (k == "sort_min_units_tile") tu.sort_min_units_tile = value > 0 ? value : dflt.sort_min_units_tile;
-    else if (k == "sort_max_rounds")
-        tu.sort_max_rounds = (value == 1 || value == 2 || value == 4 || value == 8) ? value : dflt.sort_max_rounds;
-    else return fail(RR_ERR_ARG, "unknown tuning key: " + k);
-    return RR_OK;
-}
-
-int rr_set_binning_config(int split_denominator, int min_pairs) {
-    if (split_denominator < 0 || min_pairs < 0) return fail(RR_ERR_ARG, "negative binning config");
-    Tuning& tu = tuning();
-    const Tuning dflt{};
-    tu.early_den = split_denominator == 0 ? dflt.early_den : (uint32_t)split_denominator;
-    tu.early_min = min_pairs == 0 ? dflt.early_min : (uint32_t)min_pairs;
-    return RR_OK;
-}
-
 int rr_profile_enable(int enable) {
     g_prof = enable != 0;
     return RR_OK;
@@ -1299,13 +1077,6 @@ int rr_profile_enable(int enable) {
 
 int rr_profile_select(unsigned stage_mask) {
     g_prof_mask = stage_mask;
-    return RR_OK;
-}
-
-int rr_host_wait_stats(int reset, int64_t* wait_ns, int64_t* waits) {
-    if (wait_ns) *wait_ns = g_wait_ns;
-    if (waits) *waits = g_waits;
-    if (reset) g_wait_ns = g_waits = 0;
     return RR_OK;
 }
 

@@ -18,7 +18,7 @@
 //   k_split_scan_totals  per block of Gaussians: the frame totals from the preprocess block sums
 //                        and the depth cut from sampled {depth key, pairs} (every workgroup, the
 //                        same cut; workgroup 0 publishes the frame's total pairs to the host,
-//                        rr_api.hip mailbox), then the block's {A pairs, B pairs} totals
+//                        rr_api.hip Mailbox), then the block's {A pairs, B pairs} totals
 //   k_split_scan         inclusive scan of {A pairs, B pairs} per Gaussian in index order; its last
 //                        thread leaves the phases' counts in FrameTotals (device-side only)
 //   k_sortexpand<K>    per bin: depth sort of its run + the split into its four tiles' lists
@@ -41,7 +41,7 @@ constexpr int kCutShift = kDepthKeyBits - 12;
 constexpr int kCutSamples = 4096;
 
 // Clears the image buffer's per-frame block (tile ranges, counters, open bits, bin runs and counts:
-// rr_api.hip carve_img) in a grid-stride loop, 16 B per store (a carved array: 16-B aligned).
+// rr_layout.hpp carve_img) in a grid-stride loop, 16 B per store (a carved array: 16-B aligned).
 __device__ __forceinline__ void clear_words(uint32_t* __restrict__ zero, int nzero) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x, nth = gridDim.x * blockDim.x;
     const int nv = nzero >> 2;
@@ -369,10 +369,7 @@ __global__ __launch_bounds__(256) void k_split_scan(const uint2* __restrict__ ti
     if (blockIdx.x == gridDim.x - 1 && t == 255) store_split(ft, ex);
 }
 
-// the split scan's block totals
-size_t split_scan_temp_bytes(int P) {
-    return (size_t)std::max((P + kPairScanItems - 1) / kPairScanItems, 1) * sizeof(Quad);
-}
+static_assert(sizeof(Quad) == kSplitScanTotalBytes, "rr_kernels.hpp split_scan_temp_bytes");
 
 void launch_split_scan(const uint2* tiles, const uint32_t* keys, int P, PhaseLists lists, FrameTotals* ft, void* temp,
                        int direct_blocks, uint32_t* zero, int nzero, const CutArgs& cut, hipStream_t st) {
@@ -402,8 +399,7 @@ uint32_t sx_lds_cap(int cap) {
 // scatter run kBinGroups workgroups over the same
 // strided item sets; each aggregates its items per bin in LDS, so a global atomic is paid per
 // (workgroup, bin) and not per pair (per-pair atomics on a few hot bins serialise: +40 us).
-constexpr int kBinScanMax = 16384;  // bins one workgroup holds (4K frames: 8160)
-constexpr int kBinGroups = 64;
+constexpr int kBinGroups = 64;  // (a workgroup holds up to kBinScanMax bins: rr_kernels.hpp)
 __global__ __launch_bounds__(1024) void k_bin_count(const void* __restrict__ keys_v, int wide_keys,
                                                     const uint32_t* __restrict__ n_dev, int nb,
                                                     uint32_t* __restrict__ bin_cnt) {

@@ -84,7 +84,7 @@ void launch_unpack_rows(int world, int rows_per_rank, const char* recv, size_t c
 constexpr uint32_t kDepthKeyBase = 0x3E4CCCCEu;
 constexpr int kDepthKeyBits = 27;
 
-// Early-stop binning (rr_api.hip): the tile lists are built in two phases.  Phase A bins the
+// Early-stop binning (rr_api.hip render_tiles): the tile lists are built in two phases.  Phase A bins the
 // depth-ordered pairs [0, L_A) for every tile and blends them; a tile whose pixels have all
 // saturated is final.  Phase B bins the pairs [L_A, L) only for the tiles still open and resumes
 // their blend from the state phase A left in the image buffers.  A tile's list is then
@@ -198,8 +198,12 @@ constexpr int kPairScanDirectBlocks = 512;
 // rr_bin.hip: the depth-sort-free binning
 // The phases' Gaussian lists (PhaseLists, ft->GA / GB entries) and, computed by every workgroup of
 // its first launch, the frame's totals and early-stop depth cut (published to the host mailbox);
-// the last thread leaves {LA, LB, GA, GB} in ft.  temp: split_scan_temp_bytes(P)
-size_t split_scan_temp_bytes(int P);
+// the last thread leaves {LA, LB, GA, GB} in ft.  temp: split_scan_temp_bytes(P), the blocks' totals
+constexpr size_t kSplitScanTotalBytes = 32;  // rr_bin.hip Quad
+inline size_t split_scan_temp_bytes(int P) {
+    const int nb = (P + kPairScanItems - 1) / kPairScanItems;
+    return (size_t)(nb > 1 ? nb : 1) * kSplitScanTotalBytes;
+}
 struct CutArgs {
     const uint2* block_sums;
     const uint32_t* block_wide;
@@ -220,7 +224,8 @@ void launch_sortexpand(const K* keys, const uint32_t* vals, const uint32_t* dept
 // Phase B of the gather path (rr_bin.hip k_bin_count + k_bin_scatter + k_sortexpand): the densely
 // emitted, unordered phase-B pairs (k_dup_gather) counted per bin (bin_cnt, zero on entry) and
 // dropped into their bins' runs — no bin sort.  kept: receives the pairs the bins hold.  false:
-// more bins than one workgroup scans (nothing launched).
+// more than kBinScanMax bins (nothing launched; rr_layout.hpp b_gather keeps such frames off this path).
+constexpr int kBinScanMax = 16384;  // bins one workgroup scans in LDS (4K frames: 8160)
 template <typename K>
 bool launch_sortexpand_small(int P, const K* keys, const uint32_t* vals, const uint32_t* n_dev, uint32_t* bin_cnt,
                              uint32_t* vals_sorted, const uint32_t* depth_keys, const FrameTotals* ft, int gx, int gy,
@@ -305,8 +310,7 @@ constexpr int kPointListPad = 16;
 // produced by the caller) and n_dev (device-side item count after compaction) are optional.
 // n_hint (0: n) is the expected count the unit length is chosen for when n is only a capacity
 // (units then cover n; those past the device count are empty).
-template <typename K>
-size_t radix_sort_temp_bytes(size_t n, int bits, size_t n_hint = 0);
+// temp: radix_sort_temp_bytes (rr_sort_plan.hpp, with the sort's unit geometry and RadixPlan).
 template <typename K>
 hipError_t radix_sort_pairs(void* temp, size_t temp_bytes, const K* keys_in, K* keys_out, const uint32_t* vals_in,
                             uint32_t* vals_out, size_t n, int begin_bit, int end_bit, hipStream_t st,
@@ -316,15 +320,6 @@ hipError_t radix_sort_pairs(void* temp, size_t temp_bytes, const K* keys_in, K* 
 // encoded {~start, end} (a key without items keeps {0, 0}; rr_bin.hip k_sortexpand decodes), written by
 // the last pass's scatter
 const char* radix_sort_last_error();  // which check failed in the last radix_sort_pairs call
-// Unit geometry of a sort and where its first-pass digit counts live, so that a producer kernel
-// can emit counts[digit * units + unit] for the lowest dbits0 bits itself (then pass
-// first_counts_ready = true).
-struct RadixPlan {
-    uint32_t* counts;
-    int units, unit_items, rounds, dbits0;
-};
-template <typename K>
-RadixPlan radix_sort_plan(void* temp, size_t n, int begin_bit, int end_bit, size_t n_hint = 0);
 void launch_gauss_bwd(const GaussBwdArgs& a, hipStream_t st);
 // The Gaussian-sharded multi-GPU step (rr_gauss_backward_views): one view's camera as the
 // per-Gaussian backward reads it.

@@ -25,31 +25,18 @@
 // of 4 x 7); the bits are spread evenly over the passes (13 -> 7 + 6).
 #include "rr_common.hpp"
 #include "rr_kernels.hpp"
+#include "rr_sort_plan.hpp"
 
 namespace rr {
 
 namespace {
 
-constexpr int kWaves = 4;       // waves per workgroup (unit) of the count kernel
 #ifndef RR_SORT_SW
 #define RR_SORT_SW 8
 #endif
 // waves per workgroup of the scatter (4 or 8): 8 halves each wave's serial rank rounds for the
 // same unit (depth sort 0.0913 -> 0.0877 ms/step, profiles/r03_sort_scatter8_ab.jsonl)
 constexpr int kScatterWaves = RR_SORT_SW;
-constexpr int kMaxRounds = 16;  // rounds of 64 items per wave
-constexpr int kMaxUnitItems = 64 * kWaves * kMaxRounds;  // 4096
-static_assert(kMaxUnitItems == kSortMaxUnit, "rr_kernels.hpp kSortMaxUnit");
-
-// passes of a sort of `bits` bits: 8-bit digits, or 9-bit ones for 25..27 bits (3 passes instead of
-// 4; the tile sorts, whose first-pass counts come from the duplicate's 256-digit histogram, keep
-// 8-bit digits)
-__host__ __device__ constexpr int sort_passes(int bits) {
-    return bits <= 0 ? 0 : (bits >= 25 && bits <= 27) ? 3 : (bits + 7) / 8;
-}
-__host__ __device__ constexpr int sort_max_dbits(int bits) {
-    return bits <= 0 ? 0 : (bits + sort_passes(bits) - 1) / sort_passes(bits);
-}
 
 // Items of one unit: [unit * unit_items, unit * unit_items + len).  Contiguous input has
 // len = min(unit_items, n - base) with n from the host or, when only the device knows it (a
@@ -312,78 +299,7 @@ __global__ __launch_bounds__(64 * SW) void k_rs_scatter(const K* __restrict__ ke
     }
 }
 
-struct SortLayout {
-    void* keys_alt;
-    uint32_t* vals_alt;
-    uint32_t* counts;
-    uint32_t* offsets;
-    uint32_t* totals;  // [512] per-digit totals of the current pass
-    size_t total;
-};
-
-// rounds per wave: full 16 for large inputs, fewer for small ones so that there are >= ~min_units
-// units (Tuning::sort_min_units, default 128; interleaved A/B on the bench step: with 8-bit digits
-// 512 beat 1024 by 1.7%; with the 8-wave scatter (round 3) the 3-pass depth sort of 1M keys
-// preferred its largest units: 128 (4096-item units) 0.086 vs 0.088 ms/step with 256 and 0.102
-// with 512, profiles/r03_sort_units_ab.jsonl).  Sorts of <= 16-bit keys (the bin sorts) target
-// more, smaller units (Tuning::sort_min_units_tile, default 1024): their first pass's units are the
-// duplicate's windows, whose workgroups are latency-bound (duplicate 0.098 -> 0.092, bin sort 0.087
-// -> 0.077 ms/step with 1024).  Tuning::sort_max_rounds caps the rounds (tests: 2048-item units).
-int rounds_for(size_t n, int bits) {
-    const Tuning& tu = tuning();
-    const size_t mu = (size_t)(bits <= 16 ? tu.sort_min_units_tile : tu.sort_min_units);
-    int r = std::min(tu.sort_max_rounds, kMaxRounds);
-    while (r > 1 && (n + (size_t)64 * kWaves * r - 1) / ((size_t)64 * kWaves * r) < mu) r >>= 1;
-    return r;
-}
-
-// n_hint (0: n): the size the unit length is chosen for, where n is only a capacity and the device
-// holds the count (the binning's phases: sized by the frame's pair total, filled ~1/3 and ~2/3)
-template <typename K>
-SortLayout sort_layout(void* buf, size_t n, int bits, size_t n_hint) {
-    auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-    SortLayout s{};
-    const int rounds = rounds_for(n_hint ? n_hint : n, bits);
-    const size_t units = (n + (size_t)64 * kWaves * rounds - 1) / ((size_t)64 * kWaves * rounds);
-    const int dmax = sort_max_dbits(bits);
-    const size_t nc = std::max<size_t>(((size_t)1 << dmax) * units, 1);
-    char* p = static_cast<char*>(buf);
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        void* r = p ? p + off : nullptr;
-        off = al(off + std::max<size_t>(bytes, 1));
-        return r;
-    };
-    s.keys_alt = take(n * sizeof(K));
-    s.vals_alt = static_cast<uint32_t*>(take(n * 4));
-    s.counts = static_cast<uint32_t*>(take(nc * 4));
-    s.offsets = static_cast<uint32_t*>(take(nc * 4));
-    s.totals = static_cast<uint32_t*>(take(512 * 4));
-    s.total = off;
-    return s;
-}
-
 }  // namespace
-
-template <typename K>
-size_t radix_sort_temp_bytes(size_t n, int bits, size_t n_hint) {
-    return sort_layout<K>(nullptr, n, bits, n_hint).total;
-}
-
-template <typename K>
-RadixPlan radix_sort_plan(void* temp, size_t n, int begin_bit, int end_bit, size_t n_hint) {
-    RadixPlan p{};
-    const int bits = end_bit - begin_bit;
-    if (n == 0 || bits <= 0) return p;
-    const SortLayout s = sort_layout<K>(temp, n, bits, n_hint);
-    const int passes = sort_passes(bits);
-    p.rounds = rounds_for(n_hint ? n_hint : n, bits);
-    p.unit_items = 64 * kWaves * p.rounds;
-    p.units = (int)((n + p.unit_items - 1) / p.unit_items);
-    p.dbits0 = (bits + passes - 1) / passes;
-    p.counts = s.counts;
-    return p;
-}
 
 thread_local const char* g_why = "";
 const char* radix_sort_last_error() { return g_why; }
@@ -401,8 +317,8 @@ hipError_t radix_sort_pairs(void* temp, size_t temp_bytes, const K* keys_in, K* 
     const SortLayout s = sort_layout<K>(temp, n, bits, n_hint);
     if (temp_bytes < s.total) return g_why = "temp too small", hipErrorInvalidValue;
     const int passes = sort_passes(bits);
-    const int rounds = rounds_for(n_hint ? n_hint : n, bits);
-    const int units = (int)((n + (size_t)64 * kWaves * rounds - 1) / ((size_t)64 * kWaves * rounds));
+    const RadixPlan su = sort_units(n, bits, n_hint);
+    const int rounds = su.rounds, units = su.units;
     const K* ksrc = keys_in;
     const uint32_t* vsrc = vals_in;
     int shift = begin_bit;
@@ -456,15 +372,11 @@ hipError_t radix_sort_pairs(void* temp, size_t temp_bytes, const K* keys_in, K* 
     return e;
 }
 
-template size_t radix_sort_temp_bytes<uint16_t>(size_t, int, size_t);
-template size_t radix_sort_temp_bytes<uint32_t>(size_t, int, size_t);
 template hipError_t radix_sort_pairs<uint16_t>(void*, size_t, const uint16_t*, uint16_t*, const uint32_t*, uint32_t*,
                                                size_t, int, int, hipStream_t, bool, const uint32_t*,
                                                const uint32_t*, size_t, uint2*);
 template hipError_t radix_sort_pairs<uint32_t>(void*, size_t, const uint32_t*, uint32_t*, const uint32_t*, uint32_t*,
                                                size_t, int, int, hipStream_t, bool, const uint32_t*,
                                                const uint32_t*, size_t, uint2*);
-template RadixPlan radix_sort_plan<uint16_t>(void*, size_t, int, int, size_t);
-template RadixPlan radix_sort_plan<uint32_t>(void*, size_t, int, int, size_t);
 
 }  // namespace rr

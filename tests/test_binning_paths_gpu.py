@@ -1,6 +1,6 @@
 """Every binning path of the forward (rr_api.hip render_tiles) gives the reference's per-tile
 lists: phase A by the windowed duplicate + bin sort; phase B by the gather path over its list
-(default) or by the windowed path (frames of > 16384 bins); per-bin order by the bucket sort
+(default) or by the windowed path (frames of > 16384 bins: rr_layout.hpp b_gather); per-bin order by the bucket sort
 (default) or by the LSD passes only; the phase-B gather's row masks or flat mask (frames over 128
 tiles wide), its big-Gaussian workgroup path; windows of 2048 pairs with their starts marked by the
 split scan; long runs depth-sorted in LDS or through their own output region (sx_lds_cap).  Each

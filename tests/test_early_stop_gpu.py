@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(params=["gather", "windows"])
 def split(request, monkeypatch):
     """Force the two-phase path onto small frames: phase A = L/den pairs, any frame size; phase B
-    binned by each of its two paths (rr_api.hip phase_b_gather: few pairs gathered per bin, or the
+    binned by each of its two paths (rr_layout.hpp b_gather, the phase_b_gather knob: few pairs gathered per bin, or the
     windowed duplicate + bin sort)."""
     from rain_amd import _native as N
     from rain_amd.diff_gaussian_rasterization import _C
@@ -176,7 +176,7 @@ def test_phase_b_reservation_stays_in_its_region(gpu, split):
 
 
 def test_second_render_without_a_pair_count_fails(gpu):
-    """One render per pair count (rr_api.hip g_counted_img): rendering a frame again from the same
+    """One render per pair count (rr_api.hip Handoff::counted_img): rendering a frame again from the same
     geometry call would start the gather counters where the first render's ended."""
     import ctypes
 

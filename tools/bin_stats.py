@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-bin run lengths of the bench frame's binning (1M Gaussians, 1920x1080, SH 3): the bounds
-k_bin_bounds leaves in the image buffer's cleared block (rr_api.hip carve_img), for phase A and
+k_bin_bounds leaves in the image buffer's cleared block (rr_layout.hpp carve_img), for phase A and
 phase B.  What k_sortexpand's per-bin depth sort sees: its LDS path takes runs up to kSxCap
 pairs, longer runs go through global scratch in chunks."""
 import json
@@ -20,7 +20,7 @@ def main():
     from rain_amd.diff_gaussian_rasterization import _C
 
     W, H = 1920, 1080
-    al = lambda x: (x + 255) & ~255  # noqa: E731  (rr_api.hip align_up)
+    al = lambda x: (x + 255) & ~255  # noqa: E731  (rr_layout.hpp align_up)
     N = W * H
     gx, gy = (W + 15) // 16, (H + 15) // 16
     T = gx * gy
