@@ -244,6 +244,28 @@ int rr_backward(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, 
                 const rr_grads* out, void* stream);
 
 /*
+ * Backward with gradients of the depth map and the accumulated alpha (opt-in; rr_backward gives
+ * the depth output no gradient).  The forward's depth is D(p) = sum_i alpha_i T_i z_i (z_i the
+ * view-space depth; no background term, not normalised) and the accumulated alpha is
+ * A(p) = 1 - T_final(p) = sum_i alpha_i T_i (rr_render_alpha); expected depth is D / A, formed by
+ * the caller.  dL_ddepth = dL/dD and dL_dalpha = dL/dA are [H*W] or NULL (zero).  With both NULL
+ * this is exactly rr_backward.  Otherwise dL_dpix may be NULL too (zero), and every gradient of
+ * rr_grads, the densification statistics, the fused optimizer step (rr_grads.adam) and the next
+ * frame's preprocess (rr_grads.next) see the sum of the colour, depth and alpha terms:
+ * dL/dmeans3D gains dL/dz_i times the view matrix's z row, dL/dmeans2D (NDC units) and the conic /
+ * opacity terms gain the depth and alpha parts of dL/dalpha_i.  Conventions are the colour path's
+ * (no mask for the 0.99 alpha clamp, the clamped EWA coordinate is a constant).
+ * RR_FLAG_WORKSPACE_REGISTERED is honoured as in rr_backward.
+ */
+int rr_backward_aux(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
+                    const void* geom_buffer, const void* image_buffer, const void* binning_buffer,
+                    int num_rendered, const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha,
+                    void* workspace, size_t workspace_bytes, const rr_grads* out, void* stream);
+
+/* out_alpha [H*W] = 1 - T_final of the frame last rendered into image_buffer (f: that frame). */
+int rr_render_alpha(const rr_frame* f, const void* image_buffer, float* out_alpha, void* stream);
+
+/*
  * ---- Gaussian-sharded view-parallel training step (N ranks; no reference counterpart: the
  * reference is single-GPU).  Rank r owns the Gaussian rows
  * [r*Q, (r+1)*Q) (Q a multiple of 256, N*Q >= P) and renders one view per step; the bytes that

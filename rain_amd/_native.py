@@ -100,7 +100,8 @@ RASTER_SYMBOLS = ["rr_geometry_bytes", "rr_image_bytes", "rr_binning_bytes", "rr
                   "rr_profile_select", "rr_profile_collect", "rr_stage_name", "rr_host_wait_stats", "rr_geometry_layout",
                   "rr_preprocess_rows", "rr_preprocess_rows_views", "rr_unpack_rows", "rr_forward_from_geometry",
                   "rr_forward_render_geometry",
-                  "rr_backward_records", "rr_gauss_backward_views", "rr_set_forward_workspace"]
+                  "rr_backward_records", "rr_gauss_backward_views", "rr_set_forward_workspace",
+                  "rr_backward_aux", "rr_render_alpha"]
 
 _raster = None
 _knn = None
@@ -139,6 +140,11 @@ def raster():
                                  ctypes.POINTER(sz), vp, vp, vp]
         L.rr_backward.restype = ci
         L.rr_backward.argtypes = [fp, cp, gp, vp, vp, vp, vp, ci, vp, vp, sz, ctypes.POINTER(RRGrads), vp]
+        # rr_backward plus dL_ddepth, dL_dalpha after dL_dpix (depth / accumulated-alpha gradients)
+        L.rr_backward_aux.restype = ci
+        L.rr_backward_aux.argtypes = [fp, cp, gp, vp, vp, vp, vp, ci, vp, vp, vp, vp, sz, ctypes.POINTER(RRGrads), vp]
+        L.rr_render_alpha.restype = ci
+        L.rr_render_alpha.argtypes = [fp, vp, vp, vp]
         L.rr_mark_visible.restype = ci
         L.rr_mark_visible.argtypes = [ci, vp, vp, vp, vp, vp]
         L.rr_last_error.restype = ctypes.c_char_p

@@ -589,9 +589,11 @@ int finish_forward(const rr_frame* f, const rr_camera* cam, const int* radii, vo
 }
 
 // Accumulator clear (+ the backward's tile order) and the blend backward: gacc [P][GACC_STRIDE]
-// receives every Gaussian's dmean2D / dconic / dopacity / dcolor sums of the frame.
+// receives every Gaussian's dmean2D / dconic / dopacity / dcolor sums of the frame.  With dL_ddepth or
+// dL_dalpha (rr_backward_aux) the depth / alpha variant runs and slot 9 receives dL/d(view depth).
 int blend_backward(const rr_frame* f, const rr_camera* cam, const void* geom_buffer, const void* image_buffer,
-                   const void* binning_buffer, int L, const float* dL_dpix, float* gacc, hipStream_t st) {
+                   const void* binning_buffer, int L, const float* dL_dpix, float* gacc, hipStream_t st,
+                   const float* dL_ddepth = nullptr, const float* dL_dalpha = nullptr) {
     const int P = f->P, W = f->width, H = f->height;
     const Geom gm = carve_geom(const_cast<void*>(geom_buffer), P);
     const Img im = carve_img(const_cast<void*>(image_buffer), W, H);
@@ -623,11 +625,18 @@ int blend_backward(const rr_frame* f, const rr_camera* cam, const void* geom_buf
         b.final_T = im.final_T; b.n_contrib = im.n_contrib; b.bg = cam->background; b.dL_dpix = dL_dpix;
         b.gacc = gacc;
         b.order = order;
-        launch_blend_bwd(b, st);
+        if (dL_ddepth || dL_dalpha) launch_blend_bwd_aux(b, dL_ddepth, dL_dalpha, st);
+        else launch_blend_bwd(b, st);
     }
     RR_STAGE_CHECK("blend backward");
     return RR_OK;
 }
+
+// rr_backward and rr_backward_aux (aux: dL_ddepth or dL_dalpha given; dL_dpix may then be null)
+int backward_impl(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
+                  const void* geom_buffer, const void* image_buffer, const void* binning_buffer, int num_rendered,
+                  const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha, void* workspace,
+                  size_t workspace_bytes, const rr_grads* out, void* stream);
 
 }  // namespace
 
@@ -699,11 +708,49 @@ int rr_forward(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, i
 int rr_backward(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
                 const void* geom_buffer, const void* image_buffer, const void* binning_buffer, int num_rendered,
                 const float* dL_dpix, void* workspace, size_t workspace_bytes, const rr_grads* out, void* stream) {
+    return backward_impl(f, cam, g, radii, geom_buffer, image_buffer, binning_buffer, num_rendered, dL_dpix, nullptr,
+                         nullptr, workspace, workspace_bytes, out, stream);
+}
+
+int rr_backward_aux(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
+                    const void* geom_buffer, const void* image_buffer, const void* binning_buffer, int num_rendered,
+                    const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha, void* workspace,
+                    size_t workspace_bytes, const rr_grads* out, void* stream) {
+    return backward_impl(f, cam, g, radii, geom_buffer, image_buffer, binning_buffer, num_rendered, dL_dpix, dL_ddepth,
+                         dL_dalpha, workspace, workspace_bytes, out, stream);
+}
+
+int rr_render_alpha(const rr_frame* f, const void* image_buffer, float* out_alpha, void* stream) {
+    if (!f) return fail(RR_ERR_ARG, "null frame");
+    const int P = f->P, W = f->width, H = f->height;
+    if (P < 0 || W <= 0 || H <= 0) return fail(RR_ERR_ARG, "bad P / width / height");
+    if (!out_alpha) return fail(RR_ERR_ARG, "null output buffer");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n = (size_t)W * H;
+    if (P == 0) {  // nothing was rendered: every pixel keeps T = 1
+        RR_CHECK(hipMemsetAsync(out_alpha, 0, n * sizeof(float), st), "render alpha");
+        return RR_OK;
+    }
+    if (!image_buffer) return fail(RR_ERR_ARG, "null image buffer");
+    const Img im = carve_img(const_cast<void*>(image_buffer), W, H);
+    launch_render_alpha(im.final_T, n, out_alpha, st);
+    return check(f, st, "render alpha");
+}
+
+}  // extern "C"
+
+namespace {
+
+int backward_impl(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
+                  const void* geom_buffer, const void* image_buffer, const void* binning_buffer, int num_rendered,
+                  const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha, void* workspace,
+                  size_t workspace_bytes, const rr_grads* out, void* stream) {
     int rc = validate(f, cam, g, false);
     if (rc) return rc;
     const int P = f->P, W = f->width, H = f->height, L = num_rendered;
     if (P == 0) return RR_OK;
-    if (!out || !dL_dpix || !radii || !geom_buffer || !image_buffer || !workspace)
+    const bool aux = dL_ddepth || dL_dalpha;
+    if (!out || (!dL_dpix && !aux) || !radii || !geom_buffer || !image_buffer || !workspace)
         return fail(RR_ERR_ARG, "null buffer");
     const bool raw = (f->flags & RR_FLAG_RAW_PARAMS) != 0;
     const rr_adam* ad = out->adam;
@@ -738,7 +785,9 @@ int rr_backward(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, 
     }
     hipStream_t st = (hipStream_t)stream;
     float* gacc = static_cast<float*>(workspace);
-    if (int rc2 = blend_backward(f, cam, geom_buffer, image_buffer, binning_buffer, L, dL_dpix, gacc, st)) return rc2;
+    if (int rc2 = blend_backward(f, cam, geom_buffer, image_buffer, binning_buffer, L, dL_dpix, gacc, st, dL_ddepth,
+                                 dL_dalpha))
+        return rc2;
     {
         StageTimer tm(RR_STAGE_GAUSS_BWD, st);
         GaussBwdArgs a = gauss_bwd_args(f, g, out);
@@ -760,11 +809,16 @@ int rr_backward(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, 
             a.next = n;
             a.has_next = 1;
         }
-        launch_gauss_bwd(a, st);
+        if (aux) launch_gauss_bwd_depth(a, st);
+        else launch_gauss_bwd(a, st);
     }
     RR_STAGE_CHECK("gaussian backward");
     return RR_OK;
 }
+
+}  // namespace
+
+extern "C" {
 
 int rr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix, uint8_t* present,
                     void* stream) {

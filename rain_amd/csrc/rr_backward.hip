@@ -222,7 +222,8 @@ __device__ __forceinline__ ViewCam view_cam(const GaussBwdArgs& a) {
 // stored (acc_sh false) or added (acc_sh true: the multi-view kernel sums the views in order).
 // coef == gsh (the single-view kernel) is allowed: every coefficient is read before the first
 // gradient is written.  Both are nullptr when there are neither SH inputs nor SH gradients.
-template <int DEG, bool PACKED>
+// AUX (k_gauss_bwd_depth): accumulator slot 9 holds dL/d(view depth) and joins dL/dmeans3D.
+template <int DEG, bool PACKED, bool AUX = false>
 __device__ __forceinline__ void gauss_bwd_one(const GaussBwdArgs& a, const ViewCam& c, int idx, const GaccRec& rec,
                                               const float* coef, float* gsh, bool acc_sh, SmallGrads& sg) {
     const int M = a.M;
@@ -271,6 +272,7 @@ __device__ __forceinline__ void gauss_bwd_one(const GaussBwdArgs& a, const ViewC
 
     float4 ga, gb;
     float g8;
+    [[maybe_unused]] float g9 = 0.f;
     if (PACKED) {  // 40-B record, loaded by the caller
         const float2* q = rec.q;
         const float2 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4];
@@ -281,6 +283,7 @@ __device__ __forceinline__ void gauss_bwd_one(const GaussBwdArgs& a, const ViewC
         ga = *reinterpret_cast<const float4*>(rec.gp);
         gb = *reinterpret_cast<const float4*>(rec.gp + 4);
         g8 = rec.gp[8];
+        if constexpr (AUX) g9 = rec.gp[9];
     }
     const float dm2x = ga.x, dm2y = ga.y;
     const float dcx = ga.z, dcy = ga.w, dcz = gb.x;
@@ -415,6 +418,11 @@ __device__ __forceinline__ void gauss_bwd_one(const GaussBwdArgs& a, const ViewC
     } else if (gsh && !acc_sh) {
         for (int i = 0; i < 3 * M; i++) gsh[i] = 0.f;
     }
+    if constexpr (AUX) {  // z = row 2 of the (column-major) view matrix . (mean, 1)
+        dmean.x = __builtin_fmaf(g9, c.view[2], dmean.x);
+        dmean.y = __builtin_fmaf(g9, c.view[6], dmean.y);
+        dmean.z = __builtin_fmaf(g9, c.view[10], dmean.z);
+    }
     emit3(a.dL_dmeans3D, 0, dmean);
 
     // ---- cov3D bwd (backward.cu:268-331) ----
@@ -493,7 +501,7 @@ constexpr int kShStride = 49;
 // (11 small-group values) and into s_gr (the SH gradients; s_sh keeps the coefficients), then
 // scaled by va->grad_scale (1/N, rounded like grad.mul_(1/N)) before the Adam step.
 struct GaussBwdViewsArgs;
-template <int DEG, bool MULTI, int KGB>
+template <int DEG, bool MULTI, int KGB, bool AUX = false>
 __device__ __forceinline__ void gauss_bwd_block(const GaussBwdArgs& a, const GaussBwdViewsArgs* va, float* s_sh,
                                                 float* s_gr);
 
@@ -503,6 +511,13 @@ template <int DEG>
 __global__ __launch_bounds__(kGB1) void k_gauss_bwd(GaussBwdArgs a) {
     __shared__ float s_sh[kGB1 * kShStride];
     gauss_bwd_block<DEG, false, kGB1>(a, nullptr, s_sh, s_sh);
+}
+
+// The depth / alpha backward's variant (launch_gauss_bwd_depth): the same kernel reading slot 9.
+template <int DEG>
+__global__ __launch_bounds__(kGB1) void k_gauss_bwd_depth(GaussBwdArgs a) {
+    __shared__ float s_sh[kGB1 * kShStride];
+    gauss_bwd_block<DEG, false, kGB1, true>(a, nullptr, s_sh, s_sh);
 }
 
 constexpr int kMaxViews = 16;
@@ -523,7 +538,7 @@ __global__ __launch_bounds__(kGB) void k_gauss_bwd_views(GaussBwdViewsArgs va) {
     gauss_bwd_block<DEG, true, kGB>(va.g, &va, s_sh, s_gr);
 }
 
-template <int DEG, bool MULTI, int KGB>
+template <int DEG, bool MULTI, int KGB, bool AUX>
 __device__ __forceinline__ void gauss_bwd_block(const GaussBwdArgs& a, const GaussBwdViewsArgs* va, float* s_sh,
                                                 float* s_gr) {
     const int t = threadIdx.x, lane = t & 63;
@@ -591,7 +606,7 @@ __device__ __forceinline__ void gauss_bwd_block(const GaussBwdArgs& a, const Gau
         float* row = stage ? s_sh + t * kShStride : nullptr;
         if (!MULTI) {
             const GaccRec rec{a.gacc + (size_t)idx * GACC_STRIDE, a.radii[idx], nullptr};
-            gauss_bwd_one<DEG, false>(a, view_cam(a), idx, rec, row, row, false, sg);
+            gauss_bwd_one<DEG, false, AUX>(a, view_cam(a), idx, rec, row, row, false, sg);
         } else {
             float* grow = stage ? s_gr + t * kShStride : nullptr;
             // each view's 40-B record is loaded while the previous view is processed (one record
@@ -859,7 +874,8 @@ void launch_pack_records(const float* gacc, const int* radii, int P, int Q, int 
     if (P > 0) k_pack_records<<<(P + 255) / 256, 256, 0, st>>>(gacc, radii, P, Q, chunk_rows, rec);
 }
 
-void launch_gauss_bwd(const GaussBwdArgs& a, hipStream_t st) {
+template <bool AUX>
+static void launch_gauss_bwd_impl(const GaussBwdArgs& a, hipStream_t st) {
     if (a.P == 0) return;
     if (kGB1 != 256 && a.has_next) {  // the next frame's block sums are accumulated atomically
         const size_t nbs = ((size_t)a.P + 255) / 256;
@@ -868,6 +884,15 @@ void launch_gauss_bwd(const GaussBwdArgs& a, hipStream_t st) {
     }
     // a.M <= 16 is validated by the API: the LDS row holds at most 16 coefficients
     const int nb = (a.P + kGB1 - 1) / kGB1;
+    if constexpr (AUX) {
+        switch (a.shs ? a.D : 0) {
+            case 0: k_gauss_bwd_depth<0><<<nb, kGB1, 0, st>>>(a); break;
+            case 1: k_gauss_bwd_depth<1><<<nb, kGB1, 0, st>>>(a); break;
+            case 2: k_gauss_bwd_depth<2><<<nb, kGB1, 0, st>>>(a); break;
+            default: k_gauss_bwd_depth<3><<<nb, kGB1, 0, st>>>(a); break;
+        }
+        return;
+    }
     switch (a.shs ? a.D : 0) {
         case 0: k_gauss_bwd<0><<<nb, kGB1, 0, st>>>(a); break;
         case 1: k_gauss_bwd<1><<<nb, kGB1, 0, st>>>(a); break;
@@ -875,5 +900,8 @@ void launch_gauss_bwd(const GaussBwdArgs& a, hipStream_t st) {
         default: k_gauss_bwd<3><<<nb, kGB1, 0, st>>>(a); break;
     }
 }
+
+void launch_gauss_bwd(const GaussBwdArgs& a, hipStream_t st) { launch_gauss_bwd_impl<false>(a, st); }
+void launch_gauss_bwd_depth(const GaussBwdArgs& a, hipStream_t st) { launch_gauss_bwd_impl<true>(a, st); }
 
 }  // namespace rr

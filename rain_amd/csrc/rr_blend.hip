@@ -32,9 +32,21 @@ namespace rr {
 //     -> 0.2260 / 0.2276 ms (r05_bwd_pair2_ab.jsonl);
 //   * one wave per tile: 2 or 4 waves per tile, a software-pipelined pair loop and branch-free pixel
 //     bodies all measured slower (r03_blend_bwd_waves_ab.jsonl, r03_blend_bwd_branchless_ab.jsonl).
-__global__ __launch_bounds__(64, 4) void k_blend_bwd(BlendBwdArgs a) {
+//
+// AUX (k_blend_bwd<true>, rr_backward_aux): the depth map D = sum alpha_i T_i z_i and the accumulated
+// alpha A = 1 - T_final carry gradients too (dd = dL/dD, da = dL/dA per pixel; a null map is zero).
+// Depth is one more channel of the dot product (c . dp + z dd, so R and dL/dalpha stand as
+// written), A only enters the background numerator (dA/dalpha_i = T_final / (1 - alpha_i)), and a
+// tenth component, dL/dz_i = sum alpha_i T_i dd, goes to accumulator slot 9.
+// It carries dd[PPL] and a tenth sum per pair: at the 128 VGPRs of 4 waves per SIMD it spills 9
+// registers to scratch, so it runs at 3 waves per SIMD.  The default instantiation ignores the two
+// extra arguments and compiles to the code it had before they existed.
+template <bool AUX>
+__global__ __launch_bounds__(64, AUX ? 3 : 4) void k_blend_bwd(BlendBwdArgs a, const float* __restrict__ dL_ddepth,
+                                                               const float* __restrict__ dL_dalpha_map) {
     constexpr int PPL = 4;
     constexpr int B = 64;
+    constexpr int NG = AUX ? NGRAD_AUX : NGRAD;
     const int ntiles = a.gx * a.gy;
     const int tile = a.order ? (int)a.order[blockIdx.x] : xcd_tile(blockIdx.x, ntiles);
     const int nmax = (int)a.tile_max[tile];  // pairs past this index were blended by no pixel
@@ -50,7 +62,7 @@ __global__ __launch_bounds__(64, 4) void k_blend_bwd(BlendBwdArgs a) {
     __shared__ float4 s_b2[2][B];
     __shared__ float4 s_c2[2][B];
     __shared__ uint32_t s_id2[2][B];
-    __shared__ float s_g[B * NGRAD];
+    __shared__ float s_g[B * NG];
 
     const size_t HW = (size_t)a.H * a.W;
     const float bg0 = a.bg[0], bg1 = a.bg[1], bg2 = a.bg[2];
@@ -59,6 +71,7 @@ __global__ __launch_bounds__(64, 4) void k_blend_bwd(BlendBwdArgs a) {
     // R = accum_rec . dL/dpix (8 fewer VALU ops and 4 fewer VGPRs per pixel and pair, and as well
     // conditioned as the per-channel form), advanced at each contributing pair right after its use.
     float T[PPL], tfbg[PPL], dp0[PPL], dp1[PPL], dp2[PPL], R[PPL];
+    float dd[AUX ? PPL : 1];  // dL/dD of the lane's pixels (AUX)
     int last[PPL];
 #pragma unroll
     for (int q = 0; q < PPL; q++) {
@@ -68,11 +81,22 @@ __global__ __launch_bounds__(64, 4) void k_blend_bwd(BlendBwdArgs a) {
         const float Tf = inside ? a.final_T[pix] : 0.f;
         T[q] = Tf;
         last[q] = inside ? (int)a.n_contrib[pix] : 0;
-        dp0[q] = inside ? a.dL_dpix[pix] : 0.f;
-        dp1[q] = inside ? a.dL_dpix[HW + pix] : 0.f;
-        dp2[q] = inside ? a.dL_dpix[2 * HW + pix] : 0.f;
-        // -T_final * (bg . dL/dpixel): numerator of the background term (backward.cu:521-524)
-        tfbg[q] = -Tf * (bg0 * dp0[q] + bg1 * dp1[q] + bg2 * dp2[q]);
+        if constexpr (AUX) {  // any of the three maps may be absent (zero)
+            const bool pixg = inside && a.dL_dpix;
+            dp0[q] = pixg ? a.dL_dpix[pix] : 0.f;
+            dp1[q] = pixg ? a.dL_dpix[HW + pix] : 0.f;
+            dp2[q] = pixg ? a.dL_dpix[2 * HW + pix] : 0.f;
+            dd[q] = inside && dL_ddepth ? dL_ddepth[pix] : 0.f;
+            const float da = inside && dL_dalpha_map ? dL_dalpha_map[pix] : 0.f;
+            // T_final * (dL/dA - bg . dL/dpixel): depth has no background term
+            tfbg[q] = Tf * (da - (bg0 * dp0[q] + bg1 * dp1[q] + bg2 * dp2[q]));
+        } else {
+            dp0[q] = inside ? a.dL_dpix[pix] : 0.f;
+            dp1[q] = inside ? a.dL_dpix[HW + pix] : 0.f;
+            dp2[q] = inside ? a.dL_dpix[2 * HW + pix] : 0.f;
+            // -T_final * (bg . dL/dpixel): numerator of the background term (backward.cu:521-524)
+            tfbg[q] = -Tf * (bg0 * dp0[q] + bg1 * dp1[q] + bg2 * dp2[q]);
+        }
         R[q] = 0.f;
     }
     const uint2 range = a.ranges[tile];
@@ -116,11 +140,12 @@ __global__ __launch_bounds__(64, 4) void k_blend_bwd(BlendBwdArgs a) {
         const int cnt = min(B, nmax - base);
         // two pairs per reduction (wave_sum18): each pair's pixel work in order (T and R advance
         // pair by pair), then one interleaved reduction of their 18 sums
-        auto pair_grads = [&](int j, float (&g)[NGRAD]) -> bool {
+        auto pair_grads = [&](int j, float (&g)[NG]) -> bool {
             const int contributor = nmax - 1 - (base + j);
             const float4 A = s_a[j];
             const float4 Bv = s_b[j];
             float g0, g1, g2, g3, g4, g5, g6 = 0.f, g7 = 0.f, g8 = 0.f;
+            [[maybe_unused]] float g9 = 0.f;  // AUX: dL/dz
             bool any = false;
             // The conic-side terms are linear in v = e * dL/dalpha with e = opacity G (the unclamped
             // alpha), and a lane's PPL pixels share its column (dx): per pixel only S_v, S_v.dy,
@@ -161,7 +186,11 @@ __global__ __launch_bounds__(64, 4) void k_blend_bwd(BlendBwdArgs a) {
                     const float inv = rcp_nr(1.f - alpha);
                     T[q] = T[q] * inv;                // T_i, the transmittance in front of this Gaussian
                     const float dchannel_dcolor = alpha * T[q];
-                    const float cdp = Cc.x * dp0[q] + Cc.y * dp1[q] + Cc.z * dp2[q];
+                    float cdp = Cc.x * dp0[q] + Cc.y * dp1[q] + Cc.z * dp2[q];
+                    if constexpr (AUX) {
+                        cdp = __builtin_fmaf(Bv.z, dd[q], cdp);  // the depth channel: "colour" z_i
+                        g9 = __builtin_fmaf(dchannel_dcolor, dd[q], g9);
+                    }
                     g6 += dchannel_dcolor * dp0[q];
                     g7 += dchannel_dcolor * dp1[q];
                     g8 += dchannel_dcolor * dp2[q];
@@ -196,10 +225,11 @@ __global__ __launch_bounds__(64, 4) void k_blend_bwd(BlendBwdArgs a) {
             g[6] = g6;
             g[7] = g7;
             g[8] = g8;
+            if constexpr (AUX) g[9] = g9;
             return any;
         };
         for (int j = 0; j < cnt; j += 2) {
-            float ga[NGRAD], gb[NGRAD];
+            float ga[NG], gb[NG];
             const bool anya = pair_grads(j, ga);
             const bool has_b = j + 1 < cnt;  // block-uniform
             bool anyb = false;
@@ -207,23 +237,28 @@ __global__ __launch_bounds__(64, 4) void k_blend_bwd(BlendBwdArgs a) {
                 anyb = pair_grads(j + 1, gb);
             } else {
 #pragma unroll
-                for (int k = 0; k < NGRAD; k++) gb[k] = 0.f;
+                for (int k = 0; k < NG; k++) gb[k] = 0.f;
             }
             float t[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-            if (__ballot(anya || anyb) != 0ull) wave_sum18(ga, gb, t);
-            red18_store(&s_g[j * NGRAD], lane, t, has_b);
+            if constexpr (AUX) {
+                if (__ballot(anya || anyb) != 0ull) wave_sum20(ga, gb, t);
+                red20_store(&s_g[j * NG], lane, t, has_b);
+            } else {
+                if (__ballot(anya || anyb) != 0ull) wave_sum18(ga, gb, t);
+                red18_store(&s_g[j * NGRAD], lane, t, has_b);
+            }
         }
         __syncthreads();
         // one atomic per (pair, component); consecutive lanes hit consecutive components of a pair
 #pragma unroll
-        for (int c = 0; c < NGRAD; c++) {
+        for (int c = 0; c < NG; c++) {
             const int e = c * B + t;
-            const int pair = e / NGRAD;
+            const int pair = e / NG;
             if (pair < cnt) {
                 float v = s_g[e];
-                const int comp = e - pair * NGRAD;
+                const int comp = e - pair * NG;
                 if (comp <= 1) {  // dL/dmean2D from (Sx, Sy): -(conic . S), then the NDC factor
-                    const float sx = s_g[pair * NGRAD], sy = s_g[pair * NGRAD + 1];
+                    const float sx = s_g[pair * NG], sy = s_g[pair * NG + 1];
                     float ccx, ccy, ccz;
                     splat_conic(s_a[pair], s_b[pair], ccx, ccy, ccz);
                     v = comp == 0 ? -(ccx * sx + ccy * sy) * ddelx_dx : -(ccz * sy + ccy * sx) * ddely_dy;
@@ -313,7 +348,23 @@ void launch_bwd_prologue(float* gacc, size_t nfloats, int T, const uint32_t* til
 
 void launch_blend_bwd(const BlendBwdArgs& a, hipStream_t st) {
     const int T = a.gx * a.gy;
-    if (T > 0) k_blend_bwd<<<T, 64, 0, st>>>(a);  // a.order: from the prologue or the phase-B duplicate
+    if (T > 0) k_blend_bwd<false><<<T, 64, 0, st>>>(a, nullptr, nullptr);  // a.order: from the prologue or the phase-B duplicate
+}
+
+void launch_blend_bwd_aux(const BlendBwdArgs& a, const float* dL_ddepth, const float* dL_dalpha, hipStream_t st) {
+    const int T = a.gx * a.gy;
+    if (T > 0) k_blend_bwd<true><<<T, 64, 0, st>>>(a, dL_ddepth, dL_dalpha);
+}
+
+// Accumulated alpha A = 1 - T_final of the frame last rendered into the image buffer (rr_render_alpha).
+__global__ __launch_bounds__(256) void k_render_alpha(const float* __restrict__ final_T, size_t n,
+                                                      float* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = 1.0f - final_T[i];
+}
+
+void launch_render_alpha(const float* final_T, size_t n, float* out, hipStream_t st) {
+    if (n > 0) k_render_alpha<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(final_T, n, out);
 }
 
 }  // namespace rr

@@ -12,7 +12,8 @@
 //     qb = -log2(e) conic.y, qc = -log2(e)/2 conic.z, so a pixel's alpha costs 3 fma-class ops and
 //     one exp2 of (p2 + log2 opacity) instead of the reference's 6 ops, a scaling and a multiply.
 //   * Backward accumulators: 16 floats (one 64-B line) per Gaussian, components
-//     0..1 dL/dmean2D(ndc), 2..4 dL/dconic (x,y,w), 5 dL/dopacity, 6..8 dL/dcolor.
+//     0..1 dL/dmean2D(ndc), 2..4 dL/dconic (x,y,w), 5 dL/dopacity, 6..8 dL/dcolor; slot 9 is
+//     dL/d(view depth), written and read only by the depth / alpha backward (rr_backward_aux).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -24,6 +25,7 @@ constexpr int TILE_Y = 16;
 constexpr int TILE_PIX = TILE_X * TILE_Y;  // 256 threads = 4 wave64 per tile
 constexpr int GACC_STRIDE = 16;            // floats per Gaussian in the backward accumulator
 constexpr int NGRAD = 9;                   // accumulated components per (tile, Gaussian) pair
+constexpr int NGRAD_AUX = 10;              // with depth / alpha gradients: slot 9 = dL/d(view depth)
 
 struct alignas(16) Splat {
     float4 a;
@@ -504,6 +506,26 @@ __device__ __forceinline__ void red18_store(float* dst, int lane, const float (&
 #pragma unroll
             for (int i = 0; i < 4; i++) d[2 * i + odd] = t[i];
             if (!odd) d[8] = t[4];
+        }
+    }
+}
+// The ten-component form (the depth / alpha blend backward, component 9 = dL/dz): the fifth
+// register pairs components 8 and 9 like the other four, so lane 16r+15 holds component
+// 2i + (r & 1) of pair r >> 1 in t[i] for every i < 5.
+__device__ __forceinline__ void wave_sum20(const float (&a)[NGRAD_AUX], const float (&b)[NGRAD_AUX], float (&t)[5]) {
+    float r[NGRAD_AUX];
+#pragma unroll
+    for (int k = 0; k < NGRAD_AUX; k++) r[k] = swap32_add(a[k], b[k]);
+#pragma unroll
+    for (int i = 0; i < 5; i++) t[i] = row16_sum(swap16_add(r[2 * i], r[2 * i + 1]));
+}
+__device__ __forceinline__ void red20_store(float* dst, int lane, const float (&t)[5], bool has_b) {
+    if ((lane & 15) == 15) {
+        const int row = lane >> 4, sel = row >> 1, odd = row & 1;
+        if (sel == 0 || has_b) {
+            float* d = dst + sel * NGRAD_AUX;
+#pragma unroll
+            for (int i = 0; i < 5; i++) d[2 * i + odd] = t[i];
         }
     }
 }

@@ -169,6 +169,9 @@ struct GaussBwdArgs {
     PreArgs next;
     int has_next;
 };
+// depth: the accumulators come from the depth / alpha blend backward (launch_blend_bwd_aux) —
+// slot 9, dL/d(view depth), is read and chained into dL/dmeans3D through the view matrix's z row.
+void launch_gauss_bwd_depth(const GaussBwdArgs& a, hipStream_t st);
 
 void launch_preprocess(const PreArgs& a, hipStream_t st);
 // One launch preprocessing the same rows for up to kMaxPreViews views (the Gaussian-sharded step's
@@ -291,6 +294,11 @@ void launch_blend_fwd(const BlendFwdArgs& a, hipStream_t st);
 void launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t st);
 
 void launch_blend_bwd(const BlendBwdArgs& a, hipStream_t st);  // a.order: from launch_bwd_prologue
+// The depth / alpha variant (rr_backward_aux): dL_ddepth / dL_dalpha are [H*W] per-pixel gradients of
+// the depth map and of A = 1 - T_final; either may be null (zero), and so may a.dL_dpix here.  It
+// also accumulates dL/d(view depth) into accumulator slot 9.
+void launch_blend_bwd_aux(const BlendBwdArgs& a, const float* dL_ddepth, const float* dL_dalpha, hipStream_t st);
+void launch_render_alpha(const float* final_T, size_t n, float* out, hipStream_t st);  // out = 1 - final_T
 // clears the nfloats gradient accumulators and, with order, writes the backward's tile order
 // order_flag (may be null): *order_flag == T means the order was already computed this frame
 void launch_bwd_prologue(float* gacc, size_t nfloats, int T, const uint32_t* tile_max, uint32_t* order,

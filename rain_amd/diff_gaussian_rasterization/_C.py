@@ -6,6 +6,10 @@ implemented over the C ABI in include/rain_raster.h.
 * ``rasterize_gaussians_backward``  ≙ RasterizeGaussiansBackwardCUDA  (rasterize_points.cu:110-191)
 * ``mark_visible``                  ≙ markVisible                     (rasterize_points.cu:193-212)
 
+Beyond the reference (opt-in): ``rasterize_gaussians_backward_depth`` also takes gradients of the
+depth map and of the accumulated alpha, and ``accumulated_alpha`` returns that alpha map
+(include/rain_raster.h rr_backward_aux, rr_render_alpha).
+
 Differences that are deliberate and invisible to callers: scratch buffers are sized by the C
 ABI's *_bytes() queries instead of grown through std::function callbacks; outputs the kernels
 write completely are allocated with torch.empty (the reference zero-fills them first); scratch and
@@ -139,8 +143,42 @@ def _rasterize(background, means3D, colors, opacity, scales, rotations, scale_mo
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier,
                                  cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree,
                                  campos, geomBuffer, R, binningBuffer, imageBuffer, debug, low_pass):
+    return _backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
+                     viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R,
+                     binningBuffer, imageBuffer, debug, low_pass, None, None)
+
+
+def rasterize_gaussians_backward_depth(background, means3D, radii, colors, scales, rotations, scale_modifier,
+                                       cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh,
+                                       degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, low_pass,
+                                       dL_dout_depth, dL_dout_alpha):
+    """rasterize_gaussians_backward with gradients of the depth map D = sum alpha_i T_i z_i
+    (dL_dout_depth [1,H,W]) and of the accumulated alpha A = 1 - T_final (dL_dout_alpha [1,H,W])
+    added to the colour's (no reference counterpart; rr_backward_aux).  Any of the three output
+    gradients may be an empty tensor ("absent": zero), but not all of them.  Same 8-tuple."""
+    return _backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
+                     viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R,
+                     binningBuffer, imageBuffer, debug, low_pass, dL_dout_depth, dL_dout_alpha)
+
+
+def _present(t):
+    return t is not None and t.numel() != 0
+
+
+def _backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
+              projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
+              imageBuffer, debug, low_pass, dL_dout_depth, dL_dout_alpha):
     P = means3D.size(0)
-    H, W = dL_dout_color.size(1), dL_dout_color.size(2)
+    aux = _present(dL_dout_depth) or _present(dL_dout_alpha)
+    if aux:  # the frame's size from whichever output gradient is there
+        ref = next(t for t in (dL_dout_color, dL_dout_depth, dL_dout_alpha) if _present(t))
+        H, W = ref.size(-2), ref.size(-1)
+        for name, t, c in (("dL_dout_color", dL_dout_color, NUM_CHANNELS), ("dL_dout_depth", dL_dout_depth, 1),
+                           ("dL_dout_alpha", dL_dout_alpha, 1)):
+            if _present(t) and t.numel() != c * H * W:
+                raise RuntimeError(f"{name} must have {c} x {H} x {W} elements (got {tuple(t.shape)})")
+    else:
+        H, W = dL_dout_color.size(1), dL_dout_color.size(2)
     M = sh.size(1) if sh.size(0) != 0 else 0
     device = _require_device(means3D)
     fopts = dict(dtype=torch.float32, device=device)
@@ -154,7 +192,9 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
         rotations=_dev_f32(rotations, device, "rotations"), cov3D=_dev_f32(cov3D_precomp, device, "cov3D_precomp"),
         view=_dev_f32(viewmatrix, device, "viewmatrix"), proj=_dev_f32(projmatrix, device, "projmatrix"),
         sh=_dev_f32(sh, device, "sh"), campos=_dev_f32(campos, device, "campos"),
-        dpix=_dev_f32(dL_dout_color, device, "dL_dout_color"), radii=radii.contiguous())
+        dpix=_dev_f32(dL_dout_color, device, "dL_dout_color"), radii=radii.contiguous(),
+        ddepth=_dev_f32(dL_dout_depth, device, "dL_dout_depth") if aux else None,
+        dalpha=_dev_f32(dL_dout_alpha, device, "dL_dout_alpha") if aux else None)
     # opacities are not needed by the backward (the reference does not pass them either)
     frame = _frame(P, degree, M, W, H, tan_fovx, tan_fovy, scale_modifier, low_pass, False, debug)
     cam = N.RRCamera(_ptr(keep["bg"]), _ptr(keep["view"]), _ptr(keep["proj"]), _ptr(keep["campos"]))
@@ -168,12 +208,36 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                                                "dL_dcov3D", "dL_dsh", "dL_dscales", "dL_drotations")])
     ws = torch.empty((L.rr_backward_workspace_bytes(P),), dtype=torch.uint8, device=device)
     stream = N.stream_of(means3D)
-    N.check(L.rr_backward(ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs), _ptr(keep["radii"]),
-                          _ptr(geomBuffer), _ptr(imageBuffer), _ptr(binningBuffer), int(R), _ptr(keep["dpix"]),
-                          _ptr(ws), ws.numel(), ctypes.byref(grads), stream),
-            "rasterize_gaussians_backward")
+    if aux:
+        N.check(L.rr_backward_aux(ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs), _ptr(keep["radii"]),
+                                  _ptr(geomBuffer), _ptr(imageBuffer), _ptr(binningBuffer), int(R),
+                                  _ptr(keep["dpix"]), _ptr(keep["ddepth"]), _ptr(keep["dalpha"]), _ptr(ws),
+                                  ws.numel(), ctypes.byref(grads), stream),
+                "rasterize_gaussians_backward_depth")
+    else:
+        N.check(L.rr_backward(ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs), _ptr(keep["radii"]),
+                              _ptr(geomBuffer), _ptr(imageBuffer), _ptr(binningBuffer), int(R), _ptr(keep["dpix"]),
+                              _ptr(ws), ws.numel(), ctypes.byref(grads), stream),
+                "rasterize_gaussians_backward")
     return (out["dL_dmeans2D"], out["dL_dcolors"], out["dL_dopacity"], out["dL_dmeans3D"], out["dL_dcov3D"],
             out["dL_dsh"], out["dL_dscales"], out["dL_drotations"])
+
+
+def accumulated_alpha(imageBuffer, H, W):
+    """Accumulated alpha A = 1 - T_final = sum alpha_i T_i [1,H,W] of the frame last rendered into
+    `imageBuffer` (rasterize_gaussians' imgBuffer); zeros for the empty buffer of a P == 0 frame."""
+    H, W = int(H), int(W)
+    device = _require_device(imageBuffer)
+    out = torch.zeros((1, H, W), dtype=torch.float32, device=device)
+    if imageBuffer.numel() == 0:
+        return out
+    frame = _frame(1, 0, 0, W, H, 1.0, 1.0, 1.0, 0.3, False, False)
+    L = N.raster()
+    if imageBuffer.numel() < L.rr_image_bytes(W, H):
+        raise RuntimeError("accumulated_alpha: imageBuffer is smaller than a frame of this size")
+    N.check(L.rr_render_alpha(ctypes.byref(frame), _ptr(imageBuffer), _ptr(out), N.stream_of(imageBuffer)),
+            "accumulated_alpha")
+    return out
 
 
 def mark_visible(means3D, viewmatrix, projmatrix):

@@ -99,6 +99,53 @@ class _RasterizeGaussians(torch.autograd.Function):
         return d_means3D, d_means2D, d_sh, d_colors, d_opacities, d_scales, d_rotations, d_cov3D, None
 
 
+class _RasterizeGaussiansDepth(torch.autograd.Function):
+    """_RasterizeGaussians with differentiable depth and accumulated-alpha outputs (no reference
+    counterpart; GaussianRasterizer.forward_depth): returns (color, radii, depth, alpha) with
+    depth D = sum alpha_i T_i z_i and alpha A = 1 - T_final = sum alpha_i T_i, both [1,H,W]."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                raster_settings):
+        s = raster_settings
+        args = _forward_args(s, means3D, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, sh)
+        num_rendered, color, radii, depth, geom, binning, img = _invoke(
+            _C.rasterize_gaussians, args, s.debug, "snapshot_fw.dump",
+            "\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
+        alpha = _C.accumulated_alpha(img, s.image_height, s.image_width)
+        ctx.raster_settings = s
+        ctx.num_rendered = num_rendered
+        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning,
+                              img)
+        ctx.mark_non_differentiable(radii)
+        ctx.set_materialize_grads(False)  # an output the loss does not use costs no zero fill and no work
+        return color, radii, depth, alpha
+
+    @staticmethod
+    def backward(ctx, grad_out_color, grad_radii, grad_depth, grad_alpha):
+        if grad_out_color is None and grad_depth is None and grad_alpha is None:
+            return (None,) * 9
+        s = ctx.raster_settings
+        empty = torch.Tensor([])  # "absent" (a NULL pointer in the library)
+        grad_out_color, grad_depth, grad_alpha = (empty if g is None else g
+                                                  for g in (grad_out_color, grad_depth, grad_alpha))
+        args = _backward_args(s, ctx.saved_tensors, ctx.num_rendered, grad_out_color) + (grad_depth, grad_alpha)
+        d_means2D, d_colors, d_opacities, d_means3D, d_cov3D, d_sh, d_scales, d_rotations = _invoke(
+            _C.rasterize_gaussians_backward_depth, args, s.debug, "snapshot_bw.dump",
+            "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
+        return d_means3D, d_means2D, d_sh, d_colors, d_opacities, d_scales, d_rotations, d_cov3D, None
+
+
+def _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp):
+    """The reference's two argument checks (__init__.py:177-187)."""
+    if (shs is None) == (colors_precomp is None):
+        raise Exception(_MSG_COLOR)
+    have_pair = scales is not None and rotations is not None
+    have_any = scales is not None or rotations is not None
+    if (cov3D_precomp is None and not have_pair) or (cov3D_precomp is not None and have_any):
+        raise Exception(_MSG_COV)
+
+
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings):
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
@@ -122,16 +169,24 @@ class GaussianRasterizer(nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None):
-        if (shs is None) == (colors_precomp is None):
-            raise Exception(_MSG_COLOR)
-        have_pair = scales is not None and rotations is not None
-        have_any = scales is not None or rotations is not None
-        if (cov3D_precomp is None and not have_pair) or (cov3D_precomp is not None and have_any):
-            raise Exception(_MSG_COV)
+        _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp)
         shs, colors_precomp, scales, rotations, cov3D_precomp = _absent_as_empty(shs, colors_precomp, scales,
                                                                                  rotations, cov3D_precomp)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                    cov3D_precomp, self.raster_settings)
+
+    def forward_depth(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
+                      cov3D_precomp=None):
+        """forward() with differentiable depth and accumulated alpha (opt-in; forward()'s depth gets
+        no gradient): returns (color [3,H,W], radii [P], depth [1,H,W], alpha [1,H,W]).  depth is
+        sum alpha_i T_i z_i (no background term, not normalised), alpha is 1 - T_final =
+        sum alpha_i T_i; expected depth is depth / alpha.  Gradient conventions are the colour
+        path's (no mask for the 0.99 alpha clamp, dL/dmeans2D in NDC units)."""
+        _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp)
+        shs, colors_precomp, scales, rotations, cov3D_precomp = _absent_as_empty(shs, colors_precomp, scales,
+                                                                                 rotations, cov3D_precomp)
+        return _RasterizeGaussiansDepth.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+                                              cov3D_precomp, self.raster_settings)
 
     @torch.no_grad()
     def render_depth_normal(self, means3D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None):
@@ -150,4 +205,4 @@ class GaussianRasterizer(nn.Module):
 
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "_RasterizeGaussians",
-           "_C"]
+           "_RasterizeGaussiansDepth", "_C"]

@@ -238,7 +238,8 @@ def forward_next(nxt: NextFrame, model, cache: BinningCache | None = None):
 
 
 def backward(st: RawFrame, dL_dpix: torch.Tensor, grads: dict | None, stats: tuple | None = None,
-             adam: "N.RRAdam | None" = None, dmeans2D: torch.Tensor | None = None, next_frame: NextFrame | None = None):
+             adam: "N.RRAdam | None" = None, dmeans2D: torch.Tensor | None = None, next_frame: NextFrame | None = None,
+             dL_ddepth: torch.Tensor | None = None, dL_dalpha: torch.Tensor | None = None):
     """Write dLoss/d(raw parameter) into grads['xyz'|'f_dc'|'f_rest'|'opacity'|'scaling'|'rotation']
     (contiguous fp32 tensors of the parameter shapes, fully overwritten) and, if `stats` =
     (grad_accum [P,1], denom [P,1], max_radii2D [P]) is given, update the densification statistics
@@ -247,11 +248,26 @@ def backward(st: RawFrame, dL_dpix: torch.Tensor, grads: dict | None, stats: tup
     `next_frame` (prepare_next, needs `adam`) the same pass runs that frame's preprocess on the
     stepped parameters.
     `dmeans2D` ([P,3] contiguous fp32, optional) receives the screen-space (NDC) mean gradient —
-    what the reference leaves in viewspace_points.grad — with z = 0."""
+    what the reference leaves in viewspace_points.grad — with z = 0.
+    `dL_ddepth` / `dL_dalpha` ([1,H,W] or [H,W] fp32, optional): gradients of the depth map and of the
+    accumulated alpha (accumulated_alpha()), added to the colour's in every output above, the
+    statistics, the fused step and the next frame included (rr_backward_aux); `dL_dpix` may then
+    be None."""
     if st.P == 0:
         return
     L = N.raster()
-    dpix = dL_dpix.contiguous()
+    aux = dL_ddepth is not None or dL_dalpha is not None
+    if dL_dpix is None and not aux:
+        raise RuntimeError("rain_amd.fused.backward: no output gradient given")
+    npix = st.frame.width * st.frame.height
+    maps = []
+    for name, t in (("dL_ddepth", dL_ddepth), ("dL_dalpha", dL_dalpha)):
+        if t is not None:
+            if t.dtype != torch.float32 or t.numel() != npix:
+                raise RuntimeError(f"rain_amd.fused: {name} must be a float32 [1, H, W] tensor")
+            t = t.contiguous()
+        maps.append(t)
+    dpix = dL_dpix.contiguous() if dL_dpix is not None else maps[0] if maps[0] is not None else maps[1]
     names = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation")
     if grads is None:
         if adam is None:
@@ -275,9 +291,23 @@ def backward(st: RawFrame, dL_dpix: torch.Tensor, grads: dict | None, stats: tup
         frame.flags |= N.RR_FLAG_WORKSPACE_REGISTERED
     else:
         ws = torch.empty((L.rr_backward_workspace_bytes(st.P),), dtype=torch.uint8, device=dev)
+    if aux:
+        N.check(L.rr_backward_aux(ctypes.byref(frame), ctypes.byref(st.cam), ctypes.byref(st.gs), _p(st.radii),
+                                  _p(st.geom), _p(st.img), _p(st.binning), st.num_rendered,
+                                  _p(dpix) if dL_dpix is not None else None, _p(maps[0]), _p(maps[1]), _p(ws),
+                                  ws.numel(), ctypes.byref(out), N.stream_of(dpix)), "fused backward (depth)")
+        return
     N.check(L.rr_backward(ctypes.byref(frame), ctypes.byref(st.cam), ctypes.byref(st.gs), _p(st.radii),
                           _p(st.geom), _p(st.img), _p(st.binning), st.num_rendered, _p(dpix), _p(ws), ws.numel(),
                           ctypes.byref(out), N.stream_of(dpix)), "fused backward")
+
+
+def accumulated_alpha(st: RawFrame) -> torch.Tensor:
+    """A = 1 - T_final = sum alpha_i T_i [1,H,W] of the frame `st` was rendered from."""
+    H, W = st.frame.height, st.frame.width
+    if st.P == 0:
+        return torch.zeros((1, H, W), dtype=torch.float32, device=st.radii.device)
+    return _C.accumulated_alpha(st.img, H, W)
 
 
 class RasterizeRawParams(torch.autograd.Function):
@@ -324,5 +354,46 @@ class RasterizeRawParams(torch.autograd.Function):
                      scaling=torch.empty_like(p[3]), rotation=torch.empty_like(p[4]), f_rest=torch.empty_like(p[5]))
         d2 = torch.empty((st.P, 3), dtype=torch.float32, device=p[0].device)
         backward(st, grad_color, grads, dmeans2D=d2)
+        return (grads["xyz"], grads["f_dc"], grads["f_rest"], grads["opacity"], grads["scaling"], grads["rotation"], d2,
+                None, None, None, None, None, None, None, None, None, None, None)
+
+
+class RasterizeRawParamsDepth(torch.autograd.Function):
+    """RasterizeRawParams with differentiable depth and accumulated alpha (render(depth_grad=True)):
+    returns (color, radii, depth, alpha) — depth = sum alpha_i T_i z_i, alpha = 1 - T_final, both
+    [1,H,W] — and its backward adds their gradients to the colour's (rr_backward_aux).  An output
+    the loss does not use arrives as None and goes to the library as an absent map."""
+
+    @staticmethod
+    def forward(ctx, xyz, f_dc, f_rest, opacity, scaling, rotation, means2D, sh_degree, W, H, tanfovx, tanfovy,
+                viewmatrix, projmatrix, campos, bg, low_pass, scale_modifier):
+        color, radii, depth, st = forward_params((xyz, f_dc, f_rest, opacity, scaling, rotation), sh_degree, W, H,
+                                                 tanfovx, tanfovy, viewmatrix, projmatrix, campos, bg, low_pass,
+                                                 scale_modifier)
+        alpha = accumulated_alpha(st)
+        keep, _p6 = st.keep
+        ctx.save_for_backward(xyz, f_dc, f_rest, opacity, scaling, rotation, st.radii, st.geom, st.img, st.binning,
+                              st.ws, *keep)
+        ctx.desc = (st.frame, st.cam, st.gs, st.num_rendered, st.P, st.M)
+        ctx.mark_non_differentiable(radii)
+        ctx.set_materialize_grads(False)
+        return color, radii, depth, alpha
+
+    @staticmethod
+    def backward(ctx, grad_color, _grad_radii, grad_depth, grad_alpha):
+        if grad_color is None and grad_depth is None and grad_alpha is None:
+            return (None,) * 18
+        xyz, f_dc, f_rest, opacity, scaling, rotation, radii, geom, img, binning, ws, *keep = ctx.saved_tensors
+        frame, cam, gs, num_rendered, P, M = ctx.desc
+        p = (xyz, f_dc, opacity, scaling, rotation, f_rest)  # kernel order
+        ws_first = ws if not getattr(ctx, "ws_used", False) else None
+        ctx.ws_used = True
+        st = RawFrame(frame, cam, gs, (tuple(keep), p), radii, geom, img, binning, num_rendered, P, M, ws_first)
+        grads = dict(xyz=torch.empty_like(p[0]), f_dc=torch.empty_like(p[1]), opacity=torch.empty_like(p[2]),
+                     scaling=torch.empty_like(p[3]), rotation=torch.empty_like(p[4]), f_rest=torch.empty_like(p[5]))
+        d2 = torch.empty((st.P, 3), dtype=torch.float32, device=p[0].device)
+        if st.P == 0:
+            d2.zero_()
+        backward(st, grad_color, grads, dmeans2D=d2, dL_ddepth=grad_depth, dL_dalpha=grad_alpha)
         return (grads["xyz"], grads["f_dc"], grads["f_rest"], grads["opacity"], grads["scaling"], grads["rotation"], d2,
                 None, None, None, None, None, None, None, None, None, None, None)

@@ -3,7 +3,9 @@
 Identical contract: builds GaussianRasterizationSettings from the camera, creates the
 ``means2D`` gradient sink (its .grad receives the NDC-space screen gradient), picks the SH /
 precomputed-colour and scale-rotation / precomputed-covariance inputs from the pipeline flags,
-and returns {render, viewspace_points, visibility_filter, radii, depth}.  When the model's getters
+and returns {render, viewspace_points, visibility_filter, radii, depth}.  With depth_grad=True
+(opt-in, no reference counterpart) "depth" carries gradients and the dictionary also has "alpha",
+the accumulated opacity 1 - T_final, differentiable too.  When the model's getters
 are GaussianModel's own and the pipeline flags are the defaults, the rasterizer takes the raw
 parameters and applies the getters in-kernel (rain_amd.fused.RasterizeRawParams): the same
 outputs and leaf gradients without the getters' elementwise autograd chain and the get_features
@@ -67,7 +69,7 @@ class PipelineParams:
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
-           low_pass=0.3):
+           low_pass=0.3, depth_grad=False):
     xyz = pc.get_xyz
     raw = _raw_path_ok(pc, pipe, override_color)
     if raw:
@@ -91,13 +93,17 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         sh_degree=pc.active_sh_degree, campos=viewpoint_camera.camera_center, prefiltered=False, debug=pipe.debug,
         low_pass=low_pass)
     if raw:
-        from .fused import RasterizeRawParams
+        from .fused import RasterizeRawParams, RasterizeRawParamsDepth
 
-        rendered_image, radii, depth = RasterizeRawParams.apply(
-            pc._xyz, pc._features_dc, pc._features_rest, pc._opacity, pc._scaling, pc._rotation, screenspace_points,
-            pc.active_sh_degree, raster_settings.image_width, raster_settings.image_height, tanfovx, tanfovy,
-            raster_settings.viewmatrix, raster_settings.projmatrix, raster_settings.campos, bg_color, low_pass,
-            scaling_modifier)
+        raw_args = (pc._xyz, pc._features_dc, pc._features_rest, pc._opacity, pc._scaling, pc._rotation,
+                    screenspace_points, pc.active_sh_degree, raster_settings.image_width,
+                    raster_settings.image_height, tanfovx, tanfovy, raster_settings.viewmatrix,
+                    raster_settings.projmatrix, raster_settings.campos, bg_color, low_pass, scaling_modifier)
+        if depth_grad:
+            rendered_image, radii, depth, alpha = RasterizeRawParamsDepth.apply(*raw_args)
+            return {"render": rendered_image, "viewspace_points": screenspace_points,
+                    "visibility_filter": radii > 0, "radii": radii, "depth": depth, "alpha": alpha}
+        rendered_image, radii, depth = RasterizeRawParams.apply(*raw_args)
         return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
                 "radii": radii, "depth": depth}
     rasterizer = GaussianRasterizer(raster_settings=raster_settings)
@@ -124,6 +130,12 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     else:
         colors_precomp = override_color
 
+    if depth_grad:
+        rendered_image, radii, depth, alpha = rasterizer.forward_depth(
+            means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors_precomp, opacities=opacity,
+            scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp)
+        return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
+                "radii": radii, "depth": depth, "alpha": alpha}
     rendered_image, radii, depth = rasterizer(means3D=means3D, means2D=means2D, shs=shs,
                                               colors_precomp=colors_precomp, opacities=opacity, scales=scales,
                                               rotations=rotations, cov3D_precomp=cov3D_precomp)

@@ -27,7 +27,7 @@ from collections import Counter
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-KERNEL = "_ZN2rr11k_blend_bwdENS_12BlendBwdArgsE"
+KERNEL = "_ZN2rr11k_blend_bwdILb0EEEvNS_12BlendBwdArgsEPKfS3_"  # the default (colour-only) instantiation
 
 
 def opclass(op):
