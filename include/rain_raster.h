@@ -262,6 +262,33 @@ int rr_backward_aux(const rr_frame* f, const rr_camera* cam, const rr_gaussians*
                     int num_rendered, const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha,
                     void* workspace, size_t workspace_bytes, const rr_grads* out, void* stream);
 
+/*
+ * rr_backward_aux plus a gradient of the aux normal map (RR_FLAG_AUX_NORMAL, rr_forward_render_aux):
+ * N(p) = sum_i alpha_i T_i n_i, with n_i the view-space unit normal of Gaussian i (the world axis of
+ * its smallest scale, R[:, k], rotated by the view matrix, flipped to face the camera, normalised;
+ * no background term).  dL_dnormal = dL/dN is [3,H,W] planar or NULL.  With dL_dnormal == NULL this
+ * is exactly rr_backward_aux (the same dispatch and kernels).  Otherwise dL_dpix, dL_ddepth and
+ * dL_dalpha may each be NULL (zero), and:
+ *   - the frame must carry RR_FLAG_AUX_NORMAL and geom_buffer must come from a forward
+ *     (rr_forward_geometry / rr_forward) that had the flag set: the per-Gaussian normals it wrote
+ *     there are read back;
+ *   - scales / rotations are required (not cov3D_precomp);
+ *   - dL/dalpha_i gains n_i . dL/dN(p), so opacity, position and covariance see the normal term
+ *     like the colour term (no mask for the 0.99 alpha clamp);
+ *   - dL/dn_i = sum_p alpha_i T_i dL/dN(p) reaches the rotation only, through R[:, k] and the
+ *     division by |V R[:, k]| (which matters for an unnormalised quaternion outside raw mode); the
+ *     axis index k and the flip are constants.  Scales, means3D and the camera get nothing from
+ *     n_i, and a Gaussian with a zero normal gets a zero normal gradient.
+ * Each failed condition is RR_ERR_ARG before any device work.  rr_grads.next must, as in
+ * rr_backward, name a frame WITHOUT RR_FLAG_AUX_NORMAL (this frame may carry it).  rr_grads.adam, the
+ * densification statistics and RR_FLAG_WORKSPACE_REGISTERED behave as in rr_backward_aux.
+ */
+int rr_backward_aux_normal(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
+                           const void* geom_buffer, const void* image_buffer, const void* binning_buffer,
+                           int num_rendered, const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha,
+                           const float* dL_dnormal, void* workspace, size_t workspace_bytes, const rr_grads* out,
+                           void* stream);
+
 /* out_alpha [H*W] = 1 - T_final of the frame last rendered into image_buffer (f: that frame). */
 int rr_render_alpha(const rr_frame* f, const void* image_buffer, float* out_alpha, void* stream);
 

@@ -101,7 +101,7 @@ RASTER_SYMBOLS = ["rr_geometry_bytes", "rr_image_bytes", "rr_binning_bytes", "rr
                   "rr_preprocess_rows", "rr_preprocess_rows_views", "rr_unpack_rows", "rr_forward_from_geometry",
                   "rr_forward_render_geometry",
                   "rr_backward_records", "rr_gauss_backward_views", "rr_set_forward_workspace",
-                  "rr_backward_aux", "rr_render_alpha"]
+                  "rr_backward_aux", "rr_render_alpha", "rr_backward_aux_normal"]
 
 _raster = None
 _knn = None
@@ -143,6 +143,9 @@ def raster():
         # rr_backward plus dL_ddepth, dL_dalpha after dL_dpix (depth / accumulated-alpha gradients)
         L.rr_backward_aux.restype = ci
         L.rr_backward_aux.argtypes = [fp, cp, gp, vp, vp, vp, vp, ci, vp, vp, vp, vp, sz, ctypes.POINTER(RRGrads), vp]
+        L.rr_backward_aux_normal.restype = ci
+        L.rr_backward_aux_normal.argtypes = [fp, cp, gp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, sz,
+                                             ctypes.POINTER(RRGrads), vp]
         L.rr_render_alpha.restype = ci
         L.rr_render_alpha.argtypes = [fp, vp, vp, vp]
         L.rr_mark_visible.restype = ci

@@ -590,10 +590,12 @@ int finish_forward(const rr_frame* f, const rr_camera* cam, const int* radii, vo
 
 // Accumulator clear (+ the backward's tile order) and the blend backward: gacc [P][GACC_STRIDE]
 // receives every Gaussian's dmean2D / dconic / dopacity / dcolor sums of the frame.  With dL_ddepth or
-// dL_dalpha (rr_backward_aux) the depth / alpha variant runs and slot 9 receives dL/d(view depth).
+// dL_dalpha (rr_backward_aux) the depth / alpha variant runs and slot 9 receives dL/d(view depth); with
+// dL_dnormal (rr_backward_aux_normal) the normal variant runs and slots 10..12 receive dL/d(normal).
 int blend_backward(const rr_frame* f, const rr_camera* cam, const void* geom_buffer, const void* image_buffer,
                    const void* binning_buffer, int L, const float* dL_dpix, float* gacc, hipStream_t st,
-                   const float* dL_ddepth = nullptr, const float* dL_dalpha = nullptr) {
+                   const float* dL_ddepth = nullptr, const float* dL_dalpha = nullptr,
+                   const float* dL_dnormal = nullptr) {
     const int P = f->P, W = f->width, H = f->height;
     const Geom gm = carve_geom(const_cast<void*>(geom_buffer), P);
     const Img im = carve_img(const_cast<void*>(image_buffer), W, H);
@@ -625,18 +627,20 @@ int blend_backward(const rr_frame* f, const rr_camera* cam, const void* geom_buf
         b.final_T = im.final_T; b.n_contrib = im.n_contrib; b.bg = cam->background; b.dL_dpix = dL_dpix;
         b.gacc = gacc;
         b.order = order;
-        if (dL_ddepth || dL_dalpha) launch_blend_bwd_aux(b, dL_ddepth, dL_dalpha, st);
+        if (dL_dnormal) launch_blend_bwd_normal(b, dL_ddepth, dL_dalpha, dL_dnormal, gm.normals, st);
+        else if (dL_ddepth || dL_dalpha) launch_blend_bwd_aux(b, dL_ddepth, dL_dalpha, st);
         else launch_blend_bwd(b, st);
     }
     RR_STAGE_CHECK("blend backward");
     return RR_OK;
 }
 
-// rr_backward and rr_backward_aux (aux: dL_ddepth or dL_dalpha given; dL_dpix may then be null)
+// rr_backward, rr_backward_aux and rr_backward_aux_normal (aux: dL_ddepth, dL_dalpha or dL_dnormal given;
+// dL_dpix may then be null)
 int backward_impl(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
                   const void* geom_buffer, const void* image_buffer, const void* binning_buffer, int num_rendered,
-                  const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha, void* workspace,
-                  size_t workspace_bytes, const rr_grads* out, void* stream);
+                  const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha, const float* dL_dnormal,
+                  void* workspace, size_t workspace_bytes, const rr_grads* out, void* stream);
 
 }  // namespace
 
@@ -709,7 +713,7 @@ int rr_backward(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, 
                 const void* geom_buffer, const void* image_buffer, const void* binning_buffer, int num_rendered,
                 const float* dL_dpix, void* workspace, size_t workspace_bytes, const rr_grads* out, void* stream) {
     return backward_impl(f, cam, g, radii, geom_buffer, image_buffer, binning_buffer, num_rendered, dL_dpix, nullptr,
-                         nullptr, workspace, workspace_bytes, out, stream);
+                         nullptr, nullptr, workspace, workspace_bytes, out, stream);
 }
 
 int rr_backward_aux(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
@@ -717,7 +721,16 @@ int rr_backward_aux(const rr_frame* f, const rr_camera* cam, const rr_gaussians*
                     const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha, void* workspace,
                     size_t workspace_bytes, const rr_grads* out, void* stream) {
     return backward_impl(f, cam, g, radii, geom_buffer, image_buffer, binning_buffer, num_rendered, dL_dpix, dL_ddepth,
-                         dL_dalpha, workspace, workspace_bytes, out, stream);
+                         dL_dalpha, nullptr, workspace, workspace_bytes, out, stream);
+}
+
+int rr_backward_aux_normal(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
+                           const void* geom_buffer, const void* image_buffer, const void* binning_buffer,
+                           int num_rendered, const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha,
+                           const float* dL_dnormal, void* workspace, size_t workspace_bytes, const rr_grads* out,
+                           void* stream) {
+    return backward_impl(f, cam, g, radii, geom_buffer, image_buffer, binning_buffer, num_rendered, dL_dpix, dL_ddepth,
+                         dL_dalpha, dL_dnormal, workspace, workspace_bytes, out, stream);
 }
 
 int rr_render_alpha(const rr_frame* f, const void* image_buffer, float* out_alpha, void* stream) {
@@ -743,15 +756,21 @@ namespace {
 
 int backward_impl(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
                   const void* geom_buffer, const void* image_buffer, const void* binning_buffer, int num_rendered,
-                  const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha, void* workspace,
-                  size_t workspace_bytes, const rr_grads* out, void* stream) {
+                  const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha, const float* dL_dnormal,
+                  void* workspace, size_t workspace_bytes, const rr_grads* out, void* stream) {
     int rc = validate(f, cam, g, false);
     if (rc) return rc;
     const int P = f->P, W = f->width, H = f->height, L = num_rendered;
     if (P == 0) return RR_OK;
-    const bool aux = dL_ddepth || dL_dalpha;
+    const bool aux = dL_ddepth || dL_dalpha || dL_dnormal;
     if (!out || (!dL_dpix && !aux) || !radii || !geom_buffer || !image_buffer || !workspace)
         return fail(RR_ERR_ARG, "null buffer");
+    if (dL_dnormal) {
+        if (!(f->flags & RR_FLAG_AUX_NORMAL))
+            return fail(RR_ERR_ARG, "dL_dnormal needs a frame rendered with RR_FLAG_AUX_NORMAL");
+        if (!g->scales || !g->rotations)
+            return fail(RR_ERR_ARG, "dL_dnormal needs scales/rotations (not cov3D_precomp)");
+    }
     const bool raw = (f->flags & RR_FLAG_RAW_PARAMS) != 0;
     const rr_adam* ad = out->adam;
     if (ad && !raw) return fail(RR_ERR_ARG, "the fused optimizer step needs raw-parameter mode");
@@ -786,7 +805,7 @@ int backward_impl(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g
     hipStream_t st = (hipStream_t)stream;
     float* gacc = static_cast<float*>(workspace);
     if (int rc2 = blend_backward(f, cam, geom_buffer, image_buffer, binning_buffer, L, dL_dpix, gacc, st, dL_ddepth,
-                                 dL_dalpha))
+                                 dL_dalpha, dL_dnormal))
         return rc2;
     {
         StageTimer tm(RR_STAGE_GAUSS_BWD, st);
@@ -809,7 +828,8 @@ int backward_impl(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g
             a.next = n;
             a.has_next = 1;
         }
-        if (aux) launch_gauss_bwd_depth(a, st);
+        if (dL_dnormal) launch_gauss_bwd_normal(a, st);
+        else if (aux) launch_gauss_bwd_depth(a, st);
         else launch_gauss_bwd(a, st);
     }
     RR_STAGE_CHECK("gaussian backward");

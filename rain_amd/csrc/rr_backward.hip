@@ -222,8 +222,11 @@ __device__ __forceinline__ ViewCam view_cam(const GaussBwdArgs& a) {
 // stored (acc_sh false) or added (acc_sh true: the multi-view kernel sums the views in order).
 // coef == gsh (the single-view kernel) is allowed: every coefficient is read before the first
 // gradient is written.  Both are nullptr when there are neither SH inputs nor SH gradients.
-// AUX (k_gauss_bwd_depth): accumulator slot 9 holds dL/d(view depth) and joins dL/dmeans3D.
-template <int DEG, bool PACKED, bool AUX = false>
+// AUX 1 (k_gauss_bwd_depth): accumulator slot 9 holds dL/d(view depth) and joins dL/dmeans3D.
+// AUX 2 (k_gauss_bwd_normal): slots 10..12 hold dL/dn, the gradient of the view-space unit normal
+// n = s V R[:, k] / |V R[:, k]| (gaussian_normal_parts); the axis k and the sign s are constants of
+// the forward, so it reaches the rotation only, and joins dL/dq before the raw-mode normalisation.
+template <int DEG, bool PACKED, int AUX = 0>
 __device__ __forceinline__ void gauss_bwd_one(const GaussBwdArgs& a, const ViewCam& c, int idx, const GaccRec& rec,
                                               const float* coef, float* gsh, bool acc_sh, SmallGrads& sg) {
     const int M = a.M;
@@ -273,6 +276,7 @@ __device__ __forceinline__ void gauss_bwd_one(const GaussBwdArgs& a, const ViewC
     float4 ga, gb;
     float g8;
     [[maybe_unused]] float g9 = 0.f;
+    [[maybe_unused]] v3 gn = mk(0.f, 0.f, 0.f);
     if (PACKED) {  // 40-B record, loaded by the caller
         const float2* q = rec.q;
         const float2 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4];
@@ -283,7 +287,8 @@ __device__ __forceinline__ void gauss_bwd_one(const GaussBwdArgs& a, const ViewC
         ga = *reinterpret_cast<const float4*>(rec.gp);
         gb = *reinterpret_cast<const float4*>(rec.gp + 4);
         g8 = rec.gp[8];
-        if constexpr (AUX) g9 = rec.gp[9];
+        if constexpr (AUX != 0) g9 = rec.gp[9];
+        if constexpr (AUX == 2) gn = mk(rec.gp[10], rec.gp[11], rec.gp[12]);
     }
     const float dm2x = ga.x, dm2y = ga.y;
     const float dcx = ga.z, dcy = ga.w, dcz = gb.x;
@@ -418,7 +423,7 @@ __device__ __forceinline__ void gauss_bwd_one(const GaussBwdArgs& a, const ViewC
     } else if (gsh && !acc_sh) {
         for (int i = 0; i < 3 * M; i++) gsh[i] = 0.f;
     }
-    if constexpr (AUX) {  // z = row 2 of the (column-major) view matrix . (mean, 1)
+    if constexpr (AUX != 0) {  // z = row 2 of the (column-major) view matrix . (mean, 1)
         dmean.x = __builtin_fmaf(g9, c.view[2], dmean.x);
         dmean.y = __builtin_fmaf(g9, c.view[6], dmean.y);
         dmean.z = __builtin_fmaf(g9, c.view[10], dmean.z);
@@ -464,6 +469,34 @@ __device__ __forceinline__ void gauss_bwd_one(const GaussBwdArgs& a, const ViewC
                4 * y * (Gm[2][2] + Gm[0][0]);
         dq.w = 2 * r * (Gm[0][1] - Gm[1][0]) + 2 * x * (Gm[2][0] + Gm[0][2]) + 2 * y * (Gm[1][2] + Gm[2][1]) -
                4 * z * (Gm[1][1] + Gm[0][0]);
+        if constexpr (AUX == 2) {
+            // the forward's normal (preprocess_finish): the same k, sign and |nv| from the same inputs
+            const NormalParts np = gaussian_normal_parts(scale, q, c.view, xform_point_4x3(mean, c.view));
+            if (np.len > 0.f) {
+                const float il = 1.0f / np.len;
+                const v3 n = il * np.nv;
+                // d(nv / |nv|): (g - n (n . g)) / |nv|; the flip's sign takes it back to V R[:, k]
+                const v3 dnv = (np.sign * il) * (gn - dot(n, gn) * n);
+                const v3 d = xform_vec_4x3_T(dnv, c.view);  // V^T: dL/d(R[:, k])
+                // column k of quat_rot
+                if (np.k == 0) {  // (1 - 2 (yy + zz), 2 (xy + rz), 2 (xz - ry))
+                    dq.x += 2 * (z * d.y - y * d.z);
+                    dq.y += 2 * (y * d.y + z * d.z);
+                    dq.z += 2 * (x * d.y - r * d.z) - 4 * y * d.x;
+                    dq.w += 2 * (r * d.y + x * d.z) - 4 * z * d.x;
+                } else if (np.k == 1) {  // (2 (xy - rz), 1 - 2 (xx + zz), 2 (yz + rx))
+                    dq.x += 2 * (x * d.z - z * d.x);
+                    dq.y += 2 * (y * d.x + r * d.z) - 4 * x * d.y;
+                    dq.z += 2 * (x * d.x + z * d.z);
+                    dq.w += 2 * (y * d.z - r * d.x) - 4 * z * d.y;
+                } else {  // (2 (xz + ry), 2 (yz - rx), 1 - 2 (xx + yy))
+                    dq.x += 2 * (y * d.x - x * d.y);
+                    dq.y += 2 * (z * d.x - r * d.y) - 4 * x * d.z;
+                    dq.z += 2 * (r * d.x + z * d.y) - 4 * y * d.z;
+                    dq.w += 2 * (x * d.x + y * d.y);
+                }
+            }
+        }
         if (a.raw) {
             // F.normalize backward: x / clamp_min(n, eps) -> g / n' - x (g.x) / n'^2 / n  (n >= eps)
             const float4 x = q_raw;
@@ -501,7 +534,7 @@ constexpr int kShStride = 49;
 // (11 small-group values) and into s_gr (the SH gradients; s_sh keeps the coefficients), then
 // scaled by va->grad_scale (1/N, rounded like grad.mul_(1/N)) before the Adam step.
 struct GaussBwdViewsArgs;
-template <int DEG, bool MULTI, int KGB, bool AUX = false>
+template <int DEG, bool MULTI, int KGB, int AUX = 0>
 __device__ __forceinline__ void gauss_bwd_block(const GaussBwdArgs& a, const GaussBwdViewsArgs* va, float* s_sh,
                                                 float* s_gr);
 
@@ -517,7 +550,14 @@ __global__ __launch_bounds__(kGB1) void k_gauss_bwd(GaussBwdArgs a) {
 template <int DEG>
 __global__ __launch_bounds__(kGB1) void k_gauss_bwd_depth(GaussBwdArgs a) {
     __shared__ float s_sh[kGB1 * kShStride];
-    gauss_bwd_block<DEG, false, kGB1, true>(a, nullptr, s_sh, s_sh);
+    gauss_bwd_block<DEG, false, kGB1, 1>(a, nullptr, s_sh, s_sh);
+}
+
+// The normal backward's variant (launch_gauss_bwd_normal): slots 9 and 10..12.
+template <int DEG>
+__global__ __launch_bounds__(kGB1) void k_gauss_bwd_normal(GaussBwdArgs a) {
+    __shared__ float s_sh[kGB1 * kShStride];
+    gauss_bwd_block<DEG, false, kGB1, 2>(a, nullptr, s_sh, s_sh);
 }
 
 constexpr int kMaxViews = 16;
@@ -538,7 +578,7 @@ __global__ __launch_bounds__(kGB) void k_gauss_bwd_views(GaussBwdViewsArgs va) {
     gauss_bwd_block<DEG, true, kGB>(va.g, &va, s_sh, s_gr);
 }
 
-template <int DEG, bool MULTI, int KGB, bool AUX>
+template <int DEG, bool MULTI, int KGB, int AUX>
 __device__ __forceinline__ void gauss_bwd_block(const GaussBwdArgs& a, const GaussBwdViewsArgs* va, float* s_sh,
                                                 float* s_gr) {
     const int t = threadIdx.x, lane = t & 63;
@@ -874,7 +914,7 @@ void launch_pack_records(const float* gacc, const int* radii, int P, int Q, int 
     if (P > 0) k_pack_records<<<(P + 255) / 256, 256, 0, st>>>(gacc, radii, P, Q, chunk_rows, rec);
 }
 
-template <bool AUX>
+template <int AUX>
 static void launch_gauss_bwd_impl(const GaussBwdArgs& a, hipStream_t st) {
     if (a.P == 0) return;
     if (kGB1 != 256 && a.has_next) {  // the next frame's block sums are accumulated atomically
@@ -884,7 +924,16 @@ static void launch_gauss_bwd_impl(const GaussBwdArgs& a, hipStream_t st) {
     }
     // a.M <= 16 is validated by the API: the LDS row holds at most 16 coefficients
     const int nb = (a.P + kGB1 - 1) / kGB1;
-    if constexpr (AUX) {
+    if constexpr (AUX == 2) {
+        switch (a.shs ? a.D : 0) {
+            case 0: k_gauss_bwd_normal<0><<<nb, kGB1, 0, st>>>(a); break;
+            case 1: k_gauss_bwd_normal<1><<<nb, kGB1, 0, st>>>(a); break;
+            case 2: k_gauss_bwd_normal<2><<<nb, kGB1, 0, st>>>(a); break;
+            default: k_gauss_bwd_normal<3><<<nb, kGB1, 0, st>>>(a); break;
+        }
+        return;
+    }
+    if constexpr (AUX == 1) {
         switch (a.shs ? a.D : 0) {
             case 0: k_gauss_bwd_depth<0><<<nb, kGB1, 0, st>>>(a); break;
             case 1: k_gauss_bwd_depth<1><<<nb, kGB1, 0, st>>>(a); break;
@@ -901,7 +950,8 @@ static void launch_gauss_bwd_impl(const GaussBwdArgs& a, hipStream_t st) {
     }
 }
 
-void launch_gauss_bwd(const GaussBwdArgs& a, hipStream_t st) { launch_gauss_bwd_impl<false>(a, st); }
-void launch_gauss_bwd_depth(const GaussBwdArgs& a, hipStream_t st) { launch_gauss_bwd_impl<true>(a, st); }
+void launch_gauss_bwd(const GaussBwdArgs& a, hipStream_t st) { launch_gauss_bwd_impl<0>(a, st); }
+void launch_gauss_bwd_depth(const GaussBwdArgs& a, hipStream_t st) { launch_gauss_bwd_impl<1>(a, st); }
+void launch_gauss_bwd_normal(const GaussBwdArgs& a, hipStream_t st) { launch_gauss_bwd_impl<2>(a, st); }
 
 }  // namespace rr

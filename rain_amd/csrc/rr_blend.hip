@@ -33,7 +33,7 @@ namespace rr {
 //   * one wave per tile: 2 or 4 waves per tile, a software-pipelined pair loop and branch-free pixel
 //     bodies all measured slower (r03_blend_bwd_waves_ab.jsonl, r03_blend_bwd_branchless_ab.jsonl).
 //
-// AUX (k_blend_bwd<true>, rr_backward_aux): the depth map D = sum alpha_i T_i z_i and the accumulated
+// AUX (k_blend_bwd<kBlendBwdDepth>, rr_backward_aux): the depth map D = sum alpha_i T_i z_i and the accumulated
 // alpha A = 1 - T_final carry gradients too (dd = dL/dD, da = dL/dA per pixel; a null map is zero).
 // Depth is one more channel of the dot product (c . dp + z dd, so R and dL/dalpha stand as
 // written), A only enters the background numerator (dA/dalpha_i = T_final / (1 - alpha_i)), and a
@@ -41,12 +41,29 @@ namespace rr {
 // It carries dd[PPL] and a tenth sum per pair: at the 128 VGPRs of 4 waves per SIMD it spills 9
 // registers to scratch, so it runs at 3 waves per SIMD.  The default instantiation ignores the two
 // extra arguments and compiles to the code it had before they existed.
-template <bool AUX>
-__global__ __launch_bounds__(64, AUX ? 3 : 4) void k_blend_bwd(BlendBwdArgs a, const float* __restrict__ dL_ddepth,
-                                                               const float* __restrict__ dL_dalpha_map) {
+//
+// Normal mode (k_blend_bwd<kBlendBwdNormal>, rr_backward_aux_normal): the normal map
+// N = sum alpha_i T_i n_i carries a gradient as well (dn = dL/dN per pixel, three planes; null is
+// zero).  The normal is three more channels of the dot product (c . dp + z dd + n . dn; no
+// background term, so R and the background numerator stand as written) and dL/dn_i =
+// sum alpha_i T_i dn goes to accumulator slots 10..12.  Each pair's normal record (Geom::normals,
+// 16 B) is staged beside its splat record by a fourth global -> LDS load.  It carries dn0..2[PPL] and
+// three more sums per pair: 176 VGPRs without spilling, which is 2 waves per SIMD.  Measured, 3 waves
+// per SIMD with 8 registers spilled (168 VGPRs, 36 B of scratch per lane) is the faster build:
+// blend backward 0.280 vs 0.314 ms on the bench scene, interleaved (DESIGN.md section 5,
+// profiles/normal_grad_bench.json), so it is built that way.  The other two modes ignore the two
+// extra arguments.  (The body as a shared __device__ function under two kernels, which would
+// keep the other modes' argument block at its old size, compiled them to different code.)
+enum BlendBwdMode { kBlendBwdPlain = 0, kBlendBwdDepth = 1, kBlendBwdNormal = 2 };
+template <int MODE>
+__global__ __launch_bounds__(64, MODE == kBlendBwdPlain ? 4 : 3) void k_blend_bwd(
+    BlendBwdArgs a, const float* __restrict__ dL_ddepth, const float* __restrict__ dL_dalpha_map,
+    const float* __restrict__ dL_dnormal, const float4* __restrict__ normals) {
+    constexpr bool AUX = MODE != kBlendBwdPlain;
+    constexpr bool NRM = MODE == kBlendBwdNormal;
     constexpr int PPL = 4;
     constexpr int B = 64;
-    constexpr int NG = AUX ? NGRAD_AUX : NGRAD;
+    constexpr int NG = NRM ? NGRAD_NRM : AUX ? NGRAD_AUX : NGRAD;
     const int ntiles = a.gx * a.gy;
     const int tile = a.order ? (int)a.order[blockIdx.x] : xcd_tile(blockIdx.x, ntiles);
     const int nmax = (int)a.tile_max[tile];  // pairs past this index were blended by no pixel
@@ -61,6 +78,7 @@ __global__ __launch_bounds__(64, AUX ? 3 : 4) void k_blend_bwd(BlendBwdArgs a, c
     __shared__ float4 s_a2[2][B];
     __shared__ float4 s_b2[2][B];
     __shared__ float4 s_c2[2][B];
+    __shared__ float4 s_n2[NRM ? 2 : 1][NRM ? B : 1];  // the pairs' normals (normal mode only)
     __shared__ uint32_t s_id2[2][B];
     __shared__ float s_g[B * NG];
 
@@ -72,6 +90,7 @@ __global__ __launch_bounds__(64, AUX ? 3 : 4) void k_blend_bwd(BlendBwdArgs a, c
     // conditioned as the per-channel form), advanced at each contributing pair right after its use.
     float T[PPL], tfbg[PPL], dp0[PPL], dp1[PPL], dp2[PPL], R[PPL];
     float dd[AUX ? PPL : 1];  // dL/dD of the lane's pixels (AUX)
+    float dn0[NRM ? PPL : 1], dn1[NRM ? PPL : 1], dn2[NRM ? PPL : 1];  // dL/dN of the lane's pixels
     int last[PPL];
 #pragma unroll
     for (int q = 0; q < PPL; q++) {
@@ -90,6 +109,12 @@ __global__ __launch_bounds__(64, AUX ? 3 : 4) void k_blend_bwd(BlendBwdArgs a, c
             const float da = inside && dL_dalpha_map ? dL_dalpha_map[pix] : 0.f;
             // T_final * (dL/dA - bg . dL/dpixel): depth has no background term
             tfbg[q] = Tf * (da - (bg0 * dp0[q] + bg1 * dp1[q] + bg2 * dp2[q]));
+            if constexpr (NRM) {
+                const bool nrmg = inside && dL_dnormal;
+                dn0[q] = nrmg ? dL_dnormal[pix] : 0.f;
+                dn1[q] = nrmg ? dL_dnormal[HW + pix] : 0.f;
+                dn2[q] = nrmg ? dL_dnormal[2 * HW + pix] : 0.f;
+            }
         } else {
             dp0[q] = inside ? a.dL_dpix[pix] : 0.f;
             dp1[q] = inside ? a.dL_dpix[HW + pix] : 0.f;
@@ -117,6 +142,7 @@ __global__ __launch_bounds__(64, AUX ? 3 : 4) void k_blend_bwd(BlendBwdArgs a, c
         __builtin_amdgcn_global_load_lds((gp)(src + 0), (lp)&s_a2[buf][0], 16, 0, 0);
         __builtin_amdgcn_global_load_lds((gp)(src + 1), (lp)&s_b2[buf][0], 16, 0, 0);
         __builtin_amdgcn_global_load_lds((gp)(src + 2), (lp)&s_c2[buf][0], 16, 0, 0);
+        if constexpr (NRM) __builtin_amdgcn_global_load_lds((gp)(normals + id), (lp)&s_n2[buf][0], 16, 0, 0);
     };
     // ids: lanes past the list load record 0 (staged, never read); the next round's id is loaded
     // a round ahead of its records
@@ -146,6 +172,9 @@ __global__ __launch_bounds__(64, AUX ? 3 : 4) void k_blend_bwd(BlendBwdArgs a, c
             const float4 Bv = s_b[j];
             float g0, g1, g2, g3, g4, g5, g6 = 0.f, g7 = 0.f, g8 = 0.f;
             [[maybe_unused]] float g9 = 0.f;  // AUX: dL/dz
+            [[maybe_unused]] float g10 = 0.f, g11 = 0.f, g12 = 0.f;  // NRM: dL/dn
+            [[maybe_unused]] float4 Nn = make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (NRM) Nn = s_n2[cur][j];
             bool any = false;
             // The conic-side terms are linear in v = e * dL/dalpha with e = opacity G (the unclamped
             // alpha), and a lane's PPL pixels share its column (dx): per pixel only S_v, S_v.dy,
@@ -191,6 +220,14 @@ __global__ __launch_bounds__(64, AUX ? 3 : 4) void k_blend_bwd(BlendBwdArgs a, c
                         cdp = __builtin_fmaf(Bv.z, dd[q], cdp);  // the depth channel: "colour" z_i
                         g9 = __builtin_fmaf(dchannel_dcolor, dd[q], g9);
                     }
+                    if constexpr (NRM) {  // three more channels: "colour" n_i
+                        cdp = __builtin_fmaf(Nn.x, dn0[q], cdp);
+                        cdp = __builtin_fmaf(Nn.y, dn1[q], cdp);
+                        cdp = __builtin_fmaf(Nn.z, dn2[q], cdp);
+                        g10 = __builtin_fmaf(dchannel_dcolor, dn0[q], g10);
+                        g11 = __builtin_fmaf(dchannel_dcolor, dn1[q], g11);
+                        g12 = __builtin_fmaf(dchannel_dcolor, dn2[q], g12);
+                    }
                     g6 += dchannel_dcolor * dp0[q];
                     g7 += dchannel_dcolor * dp1[q];
                     g8 += dchannel_dcolor * dp2[q];
@@ -226,6 +263,11 @@ __global__ __launch_bounds__(64, AUX ? 3 : 4) void k_blend_bwd(BlendBwdArgs a, c
             g[7] = g7;
             g[8] = g8;
             if constexpr (AUX) g[9] = g9;
+            if constexpr (NRM) {
+                g[10] = g10;
+                g[11] = g11;
+                g[12] = g12;
+            }
             return any;
         };
         for (int j = 0; j < cnt; j += 2) {
@@ -239,13 +281,19 @@ __global__ __launch_bounds__(64, AUX ? 3 : 4) void k_blend_bwd(BlendBwdArgs a, c
 #pragma unroll
                 for (int k = 0; k < NG; k++) gb[k] = 0.f;
             }
-            float t[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-            if constexpr (AUX) {
-                if (__ballot(anya || anyb) != 0ull) wave_sum20(ga, gb, t);
-                red20_store(&s_g[j * NG], lane, t, has_b);
+            if constexpr (NRM) {
+                float t[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                if (__ballot(anya || anyb) != 0ull) wave_sum26(ga, gb, t);
+                red26_store(&s_g[j * NG], lane, t, has_b);
             } else {
-                if (__ballot(anya || anyb) != 0ull) wave_sum18(ga, gb, t);
-                red18_store(&s_g[j * NGRAD], lane, t, has_b);
+                float t[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+                if constexpr (AUX) {
+                    if (__ballot(anya || anyb) != 0ull) wave_sum20(ga, gb, t);
+                    red20_store(&s_g[j * NG], lane, t, has_b);
+                } else {
+                    if (__ballot(anya || anyb) != 0ull) wave_sum18(ga, gb, t);
+                    red18_store(&s_g[j * NGRAD], lane, t, has_b);
+                }
             }
         }
         __syncthreads();
@@ -348,12 +396,19 @@ void launch_bwd_prologue(float* gacc, size_t nfloats, int T, const uint32_t* til
 
 void launch_blend_bwd(const BlendBwdArgs& a, hipStream_t st) {
     const int T = a.gx * a.gy;
-    if (T > 0) k_blend_bwd<false><<<T, 64, 0, st>>>(a, nullptr, nullptr);  // a.order: from the prologue or the phase-B duplicate
+    // a.order: from the prologue or the phase-B duplicate
+    if (T > 0) k_blend_bwd<kBlendBwdPlain><<<T, 64, 0, st>>>(a, nullptr, nullptr, nullptr, nullptr);
 }
 
 void launch_blend_bwd_aux(const BlendBwdArgs& a, const float* dL_ddepth, const float* dL_dalpha, hipStream_t st) {
     const int T = a.gx * a.gy;
-    if (T > 0) k_blend_bwd<true><<<T, 64, 0, st>>>(a, dL_ddepth, dL_dalpha);
+    if (T > 0) k_blend_bwd<kBlendBwdDepth><<<T, 64, 0, st>>>(a, dL_ddepth, dL_dalpha, nullptr, nullptr);
+}
+
+void launch_blend_bwd_normal(const BlendBwdArgs& a, const float* dL_ddepth, const float* dL_dalpha,
+                             const float* dL_dnormal, const float4* normals, hipStream_t st) {
+    const int T = a.gx * a.gy;
+    if (T > 0) k_blend_bwd<kBlendBwdNormal><<<T, 64, 0, st>>>(a, dL_ddepth, dL_dalpha, dL_dnormal, normals);
 }
 
 // Accumulated alpha A = 1 - T_final of the frame last rendered into the image buffer (rr_render_alpha).

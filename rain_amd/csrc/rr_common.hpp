@@ -13,7 +13,9 @@
 //     one exp2 of (p2 + log2 opacity) instead of the reference's 6 ops, a scaling and a multiply.
 //   * Backward accumulators: 16 floats (one 64-B line) per Gaussian, components
 //     0..1 dL/dmean2D(ndc), 2..4 dL/dconic (x,y,w), 5 dL/dopacity, 6..8 dL/dcolor; slot 9 is
-//     dL/d(view depth), written and read only by the depth / alpha backward (rr_backward_aux).
+//     dL/d(view depth), written and read only by the depth / alpha backward (rr_backward_aux);
+//     slots 10..12 are dL/d(view-space unit normal), only with a normal gradient
+//     (rr_backward_aux_normal).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -26,6 +28,7 @@ constexpr int TILE_PIX = TILE_X * TILE_Y;  // 256 threads = 4 wave64 per tile
 constexpr int GACC_STRIDE = 16;            // floats per Gaussian in the backward accumulator
 constexpr int NGRAD = 9;                   // accumulated components per (tile, Gaussian) pair
 constexpr int NGRAD_AUX = 10;              // with depth / alpha gradients: slot 9 = dL/d(view depth)
+constexpr int NGRAD_NRM = 13;              // with a normal gradient too: slots 10..12 = dL/d(normal)
 
 struct alignas(16) Splat {
     float4 a;
@@ -244,7 +247,15 @@ __device__ __forceinline__ void quat_rot(float4 q, float R[3][3]) {
 // normals): the world axis of the Gaussian's smallest scale (a column of R), rotated into view
 // space, flipped to face the camera, unit length.  Same op order as gaussian_normal in
 // oracle/raster_oracle.c.
-__device__ __forceinline__ float4 gaussian_normal(v3 sc, float4 q, const float* view, v3 p_view) {
+// gaussian_normal_parts holds what the forward and the normal backward (rr_backward.hip) share:
+// the axis index k, the flipped view-space axis nv, the flip's sign and |nv|.
+struct NormalParts {
+    int k;       // index of the smallest scale (strict comparisons: ties keep the lower index)
+    v3 nv;       // V R[:, k], negated when it faced away from the camera
+    float sign;  // -1 if negated, else 1
+    float len;   // |nv| (1 for a unit quaternion)
+};
+__device__ __forceinline__ NormalParts gaussian_normal_parts(v3 sc, float4 q, const float* view, v3 p_view) {
     float R[3][3];
     quat_rot(q, R);
     int k = 0;
@@ -254,8 +265,18 @@ __device__ __forceinline__ float4 gaussian_normal(v3 sc, float4 q, const float* 
                                                                  : mk(R[0][2], R[1][2], R[2][2]);
     v3 nv = mk(view[0] * n.x + view[4] * n.y + view[8] * n.z, view[1] * n.x + view[5] * n.y + view[9] * n.z,
                view[2] * n.x + view[6] * n.y + view[10] * n.z);
-    if (dot(nv, p_view) > 0.f) nv = mk(-nv.x, -nv.y, -nv.z);
+    float sign = 1.f;
+    if (dot(nv, p_view) > 0.f) {
+        nv = mk(-nv.x, -nv.y, -nv.z);
+        sign = -1.f;
+    }
     const float len = sqrtf(dot(nv, nv));
+    return NormalParts{k, nv, sign, len};
+}
+__device__ __forceinline__ float4 gaussian_normal(v3 sc, float4 q, const float* view, v3 p_view) {
+    const NormalParts p = gaussian_normal_parts(sc, q, view, p_view);
+    const v3 nv = p.nv;
+    const float len = p.len;
     return len > 0.f ? make_float4(nv.x / len, nv.y / len, nv.z / len, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
@@ -526,6 +547,28 @@ __device__ __forceinline__ void red20_store(float* dst, int lane, const float (&
             float* d = dst + sel * NGRAD_AUX;
 #pragma unroll
             for (int i = 0; i < 5; i++) d[2 * i + odd] = t[i];
+        }
+    }
+}
+// The thirteen-component form (the normal blend backward, components 10..12 = dL/dn): padded to 14,
+// so lane 16r+15 holds component 2i + (r & 1) of pair r >> 1 in t[i] for i < 6, and the even rows
+// (lanes 15 / 47) hold component 12 of a / b in t[6].
+__device__ __forceinline__ void wave_sum26(const float (&a)[NGRAD_NRM], const float (&b)[NGRAD_NRM], float (&t)[7]) {
+    float r[NGRAD_NRM];
+#pragma unroll
+    for (int k = 0; k < NGRAD_NRM; k++) r[k] = swap32_add(a[k], b[k]);
+#pragma unroll
+    for (int i = 0; i < 6; i++) t[i] = row16_sum(swap16_add(r[2 * i], r[2 * i + 1]));
+    t[6] = row16_sum(swap16_add(r[12], 0.f));
+}
+__device__ __forceinline__ void red26_store(float* dst, int lane, const float (&t)[7], bool has_b) {
+    if ((lane & 15) == 15) {
+        const int row = lane >> 4, sel = row >> 1, odd = row & 1;
+        if (sel == 0 || has_b) {
+            float* d = dst + sel * NGRAD_NRM;
+#pragma unroll
+            for (int i = 0; i < 6; i++) d[2 * i + odd] = t[i];
+            if (!odd) d[12] = t[6];
         }
     }
 }

@@ -172,6 +172,9 @@ struct GaussBwdArgs {
 // depth: the accumulators come from the depth / alpha blend backward (launch_blend_bwd_aux) —
 // slot 9, dL/d(view depth), is read and chained into dL/dmeans3D through the view matrix's z row.
 void launch_gauss_bwd_depth(const GaussBwdArgs& a, hipStream_t st);
+// normal: the accumulators come from launch_blend_bwd_normal — slot 9 as above, and slots 10..12,
+// dL/d(view-space unit normal), are chained into dL/drotations (a.scales / a.rotations required).
+void launch_gauss_bwd_normal(const GaussBwdArgs& a, hipStream_t st);
 
 void launch_preprocess(const PreArgs& a, hipStream_t st);
 // One launch preprocessing the same rows for up to kMaxPreViews views (the Gaussian-sharded step's
@@ -298,6 +301,12 @@ void launch_blend_bwd(const BlendBwdArgs& a, hipStream_t st);  // a.order: from 
 // the depth map and of A = 1 - T_final; either may be null (zero), and so may a.dL_dpix here.  It
 // also accumulates dL/d(view depth) into accumulator slot 9.
 void launch_blend_bwd_aux(const BlendBwdArgs& a, const float* dL_ddepth, const float* dL_dalpha, hipStream_t st);
+// The normal variant (rr_backward_aux_normal): dL_dnormal is the [3,H,W] planar gradient of the aux
+// normal map (any of the four maps may be null), normals the frame's per-Gaussian view-space
+// normals (Geom::normals, written by a forward with RR_FLAG_AUX_NORMAL).  It also accumulates
+// dL/d(normal) into accumulator slots 10..12.
+void launch_blend_bwd_normal(const BlendBwdArgs& a, const float* dL_ddepth, const float* dL_dalpha,
+                             const float* dL_dnormal, const float4* normals, hipStream_t st);
 void launch_render_alpha(const float* final_T, size_t n, float* out, hipStream_t st);  // out = 1 - final_T
 // clears the nfloats gradient accumulators and, with order, writes the backward's tile order
 // order_flag (may be null): *order_flag == T means the order was already computed this frame

@@ -8,7 +8,8 @@ implemented over the C ABI in include/rain_raster.h.
 
 Beyond the reference (opt-in): ``rasterize_gaussians_backward_depth`` also takes gradients of the
 depth map and of the accumulated alpha, and ``accumulated_alpha`` returns that alpha map
-(include/rain_raster.h rr_backward_aux, rr_render_alpha).
+(include/rain_raster.h rr_backward_aux, rr_render_alpha); ``rasterize_gaussians_backward_normal``
+takes a gradient of the aux normal map of ``rasterize_gaussians_aux`` as well (rr_backward_aux_normal).
 
 Differences that are deliberate and invisible to callers: scratch buffers are sized by the C
 ABI's *_bytes() queries instead of grown through std::function callbacks; outputs the kernels
@@ -161,20 +162,37 @@ def rasterize_gaussians_backward_depth(background, means3D, radii, colors, scale
                      binningBuffer, imageBuffer, debug, low_pass, dL_dout_depth, dL_dout_alpha)
 
 
+def rasterize_gaussians_backward_normal(background, means3D, radii, colors, scales, rotations, scale_modifier,
+                                        cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh,
+                                        degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, low_pass,
+                                        dL_dout_depth, dL_dout_alpha, dL_dout_normal):
+    """rasterize_gaussians_backward_depth plus a gradient of the aux normal map N = sum alpha_i T_i n_i
+    (dL_dout_normal [3,H,W]; rr_backward_aux_normal).  The buffers must come from
+    rasterize_gaussians_aux (its geomBuffer holds the per-Gaussian normals).  Any of the four output
+    gradients may be an empty tensor ("absent": zero), but not all of them; with dL_dout_normal
+    absent this is rasterize_gaussians_backward_depth.  The normal reaches dL_drotations directly and
+    every geometric gradient through alpha_i; scales, means3D and the camera get nothing from n_i
+    itself (the axis choice and the flip towards the camera are constants).  Same 8-tuple."""
+    return _backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
+                     viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R,
+                     binningBuffer, imageBuffer, debug, low_pass, dL_dout_depth, dL_dout_alpha, dL_dout_normal)
+
+
 def _present(t):
     return t is not None and t.numel() != 0
 
 
 def _backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
               projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
-              imageBuffer, debug, low_pass, dL_dout_depth, dL_dout_alpha):
+              imageBuffer, debug, low_pass, dL_dout_depth, dL_dout_alpha, dL_dout_normal=None):
     P = means3D.size(0)
-    aux = _present(dL_dout_depth) or _present(dL_dout_alpha)
+    nrm = _present(dL_dout_normal)
+    aux = _present(dL_dout_depth) or _present(dL_dout_alpha) or nrm
     if aux:  # the frame's size from whichever output gradient is there
-        ref = next(t for t in (dL_dout_color, dL_dout_depth, dL_dout_alpha) if _present(t))
+        ref = next(t for t in (dL_dout_color, dL_dout_depth, dL_dout_alpha, dL_dout_normal) if _present(t))
         H, W = ref.size(-2), ref.size(-1)
         for name, t, c in (("dL_dout_color", dL_dout_color, NUM_CHANNELS), ("dL_dout_depth", dL_dout_depth, 1),
-                           ("dL_dout_alpha", dL_dout_alpha, 1)):
+                           ("dL_dout_alpha", dL_dout_alpha, 1), ("dL_dout_normal", dL_dout_normal, 3)):
             if _present(t) and t.numel() != c * H * W:
                 raise RuntimeError(f"{name} must have {c} x {H} x {W} elements (got {tuple(t.shape)})")
     else:
@@ -194,9 +212,12 @@ def _backward(background, means3D, radii, colors, scales, rotations, scale_modif
         sh=_dev_f32(sh, device, "sh"), campos=_dev_f32(campos, device, "campos"),
         dpix=_dev_f32(dL_dout_color, device, "dL_dout_color"), radii=radii.contiguous(),
         ddepth=_dev_f32(dL_dout_depth, device, "dL_dout_depth") if aux else None,
-        dalpha=_dev_f32(dL_dout_alpha, device, "dL_dout_alpha") if aux else None)
+        dalpha=_dev_f32(dL_dout_alpha, device, "dL_dout_alpha") if aux else None,
+        dnormal=_dev_f32(dL_dout_normal, device, "dL_dout_normal") if nrm else None)
     # opacities are not needed by the backward (the reference does not pass them either)
     frame = _frame(P, degree, M, W, H, tan_fovx, tan_fovy, scale_modifier, low_pass, False, debug)
+    if nrm:  # the forward was rasterize_gaussians_aux
+        frame.flags |= N.RR_FLAG_AUX_NORMAL
     cam = N.RRCamera(_ptr(keep["bg"]), _ptr(keep["view"]), _ptr(keep["proj"]), _ptr(keep["campos"]))
     gs = N.RRGaussians(_ptr(keep["means3D"]), _ptr(keep["sh"]), _ptr(keep["colors"]), None,
                        _ptr(keep["scales"]), _ptr(keep["rotations"]), _ptr(keep["cov3D"]))
@@ -208,7 +229,14 @@ def _backward(background, means3D, radii, colors, scales, rotations, scale_modif
                                                "dL_dcov3D", "dL_dsh", "dL_dscales", "dL_drotations")])
     ws = torch.empty((L.rr_backward_workspace_bytes(P),), dtype=torch.uint8, device=device)
     stream = N.stream_of(means3D)
-    if aux:
+    if nrm:
+        N.check(L.rr_backward_aux_normal(ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs),
+                                         _ptr(keep["radii"]), _ptr(geomBuffer), _ptr(imageBuffer),
+                                         _ptr(binningBuffer), int(R), _ptr(keep["dpix"]), _ptr(keep["ddepth"]),
+                                         _ptr(keep["dalpha"]), _ptr(keep["dnormal"]), _ptr(ws), ws.numel(),
+                                         ctypes.byref(grads), stream),
+                "rasterize_gaussians_backward_normal")
+    elif aux:
         N.check(L.rr_backward_aux(ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs), _ptr(keep["radii"]),
                                   _ptr(geomBuffer), _ptr(imageBuffer), _ptr(binningBuffer), int(R),
                                   _ptr(keep["dpix"]), _ptr(keep["ddepth"]), _ptr(keep["dalpha"]), _ptr(ws),

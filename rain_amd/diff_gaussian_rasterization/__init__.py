@@ -19,6 +19,7 @@ from . import _C
 
 _MSG_COLOR = 'Please provide excatly one of either SHs or precomputed colors!'  # reference text, typo included
 _MSG_COV = 'Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!'
+_MSG_NORMAL = 'render_depth_normal needs the scale/rotation pair (normals come from the scale axes)'
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -136,6 +137,44 @@ class _RasterizeGaussiansDepth(torch.autograd.Function):
         return d_means3D, d_means2D, d_sh, d_colors, d_opacities, d_scales, d_rotations, d_cov3D, None
 
 
+class _RasterizeGaussiansNormal(torch.autograd.Function):
+    """_RasterizeGaussiansDepth plus a differentiable aux normal map (no reference counterpart;
+    GaussianRasterizer.forward_normal): returns (color, radii, depth, alpha, normal) with
+    normal N = sum alpha_i T_i n_i [3,H,W] (render_depth_normal's map)."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                raster_settings):
+        s = raster_settings
+        args = _forward_args(s, means3D, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, sh)
+        num_rendered, color, radii, depth, normal, geom, binning, img = _invoke(
+            _C.rasterize_gaussians_aux, args, s.debug, "snapshot_fw.dump",
+            "\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
+        alpha = _C.accumulated_alpha(img, s.image_height, s.image_width)
+        ctx.raster_settings = s
+        ctx.num_rendered = num_rendered
+        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning,
+                              img)
+        ctx.mark_non_differentiable(radii)
+        ctx.set_materialize_grads(False)
+        return color, radii, depth, alpha, normal
+
+    @staticmethod
+    def backward(ctx, grad_out_color, grad_radii, grad_depth, grad_alpha, grad_normal):
+        if grad_out_color is None and grad_depth is None and grad_alpha is None and grad_normal is None:
+            return (None,) * 9
+        s = ctx.raster_settings
+        empty = torch.Tensor([])  # "absent" (a NULL pointer in the library)
+        grad_out_color, grad_depth, grad_alpha, grad_normal = (
+            empty if g is None else g for g in (grad_out_color, grad_depth, grad_alpha, grad_normal))
+        args = _backward_args(s, ctx.saved_tensors, ctx.num_rendered, grad_out_color) + (grad_depth, grad_alpha,
+                                                                                        grad_normal)
+        d_means2D, d_colors, d_opacities, d_means3D, d_cov3D, d_sh, d_scales, d_rotations = _invoke(
+            _C.rasterize_gaussians_backward_normal, args, s.debug, "snapshot_bw.dump",
+            "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
+        return d_means3D, d_means2D, d_sh, d_colors, d_opacities, d_scales, d_rotations, d_cov3D, None
+
+
 def _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp):
     """The reference's two argument checks (__init__.py:177-187)."""
     if (shs is None) == (colors_precomp is None):
@@ -188,6 +227,22 @@ class GaussianRasterizer(nn.Module):
         return _RasterizeGaussiansDepth.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                               cov3D_precomp, self.raster_settings)
 
+    def forward_normal(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
+                       cov3D_precomp=None):
+        """forward_depth() plus a differentiable aux normal map (opt-in): returns (color [3,H,W],
+        radii [P], depth [1,H,W], alpha [1,H,W], normal [3,H,W]).  normal is render_depth_normal's map,
+        sum alpha_i T_i n_i with n_i the view-space unit normal (the smallest-scale axis, facing the
+        camera; no background term).  Its gradient reaches the rotations directly (the axis choice
+        and the flip are constants) and opacity, position and covariance through alpha_i.  Needs the
+        scale/rotation pair (cov3D_precomp is refused)."""
+        _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp)
+        if cov3D_precomp is not None:
+            raise Exception(_MSG_NORMAL)
+        shs, colors_precomp, scales, rotations, cov3D_precomp = _absent_as_empty(shs, colors_precomp, scales,
+                                                                                 rotations, cov3D_precomp)
+        return _RasterizeGaussiansNormal.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+                                               cov3D_precomp, self.raster_settings)
+
     @torch.no_grad()
     def render_depth_normal(self, means3D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None):
         """Forward only, with the auxiliary outputs of BASELINE configs[4]: returns (color [3,H,W],
@@ -197,7 +252,7 @@ class GaussianRasterizer(nn.Module):
         if (shs is None) == (colors_precomp is None):
             raise Exception(_MSG_COLOR)
         if scales is None or rotations is None:
-            raise Exception('render_depth_normal needs the scale/rotation pair (normals come from the scale axes)')
+            raise Exception(_MSG_NORMAL)
         shs, colors_precomp, cov3D = _absent_as_empty(shs, colors_precomp, None)
         args = _forward_args(self.raster_settings, means3D, colors_precomp, opacities, scales, rotations, cov3D, shs)
         out = _C.rasterize_gaussians_aux(*args)
@@ -205,4 +260,4 @@ class GaussianRasterizer(nn.Module):
 
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "_RasterizeGaussians",
-           "_RasterizeGaussiansDepth", "_C"]
+           "_RasterizeGaussiansDepth", "_RasterizeGaussiansNormal", "_C"]

@@ -43,6 +43,8 @@ class RawFrame:
     # the backward's accumulator workspace, zero-filled by the forward render
     # (rr_set_forward_workspace); the first backward uses it, a second one allocates its own
     ws: torch.Tensor | None = None
+    # the aux normal map [3,H,W] of a frame rendered with normal=True (RR_FLAG_AUX_NORMAL), else None
+    normal: torch.Tensor | None = None
 
 
 class BinningCache:
@@ -62,24 +64,27 @@ class BinningCache:
 
 
 def forward(model, camera, bg: torch.Tensor, low_pass: float, scale_modifier: float = 1.0,
-            cache: BinningCache | None = None):
+            cache: BinningCache | None = None, normal: bool = False):
     """Render `camera` from `model` (a GaussianModel) in raw-parameter mode.
     Returns (color [3,H,W], radii [P] int32, depth [1,H,W], RawFrame).  With `cache` the binning
     buffer is reused (see BinningCache) and must not be needed by an earlier frame's pending
-    backward."""
+    backward.  With `normal` the frame also renders the aux normal map (RR_FLAG_AUX_NORMAL), left in
+    the RawFrame's `normal` field ([3,H,W]); backward(dL_dnormal=...) differentiates it.  Such a
+    frame always runs its own preprocess (it cannot be the `next_frame` of an earlier backward)."""
     params = (model._xyz, model._features_dc, model._features_rest, model._opacity, model._scaling,
               model._rotation)
     return forward_params(params, model.active_sh_degree, int(camera.image_width), int(camera.image_height),
                           math.tan(camera.FoVx * 0.5), math.tan(camera.FoVy * 0.5), camera.world_view_transform,
-                          camera.full_proj_transform, camera.camera_center, bg, low_pass, scale_modifier, cache)
+                          camera.full_proj_transform, camera.camera_center, bg, low_pass, scale_modifier, cache,
+                          normal)
 
 
 def forward_params(params, sh_degree: int, W: int, H: int, tanfovx: float, tanfovy: float, viewmatrix, projmatrix,
                    campos, bg: torch.Tensor, low_pass: float, scale_modifier: float = 1.0,
-                   cache: BinningCache | None = None):
+                   cache: BinningCache | None = None, normal: bool = False):
     """forward() on explicit raw parameters (xyz, f_dc, f_rest, opacity, scaling, rotation) — the
     GaussianModel attributes before activation — and camera values as render() puts them in
-    GaussianRasterizationSettings."""
+    GaussianRasterizationSettings.  `normal`: see forward()."""
     xyz = params[0]
     dev = xyz.device
     if dev.type != "cuda":
@@ -90,7 +95,7 @@ def forward_params(params, sh_degree: int, W: int, H: int, tanfovx: float, tanfo
     M = 1 + f_rest.shape[1]
     D = int(sh_degree)
     L = N.raster()
-    flags = N.RR_FLAG_RAW_PARAMS | _C.frame_flags()
+    flags = N.RR_FLAG_RAW_PARAMS | _C.frame_flags() | (N.RR_FLAG_AUX_NORMAL if normal else 0)
     frame = N.RRFrame(P, D, M, W, H, float(tanfovx), float(tanfovy), float(scale_modifier), float(low_pass), 0, 0,
                       flags)
     keep = (bg.contiguous(), viewmatrix.contiguous(), projmatrix.contiguous(), campos.contiguous())
@@ -112,7 +117,9 @@ def forward_params(params, sh_degree: int, W: int, H: int, tanfovx: float, tanfo
     stream = N.stream_of(xyz)
     nr, npairs = ctypes.c_int(0), ctypes.c_int(0)
     ws = _register_workspace(L, P, dev)
-    if P > 0 and cache is not None:
+    # the aux normal frame goes through the two-stage calls (rr_forward renders no normal map)
+    nmap = torch.empty((3, H, W), **fo) if normal else None
+    if P > 0 and cache is not None and not normal:
         binning = cache.buf if cache.buf is not None and cache.buf.device == dev else torch.empty((0,), **u8)
         need = ctypes.c_size_t(0)
         rc = L.rr_forward(ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs), _p(radii), _p(geom), geom.numel(),
@@ -130,15 +137,19 @@ def forward_params(params, sh_degree: int, W: int, H: int, tanfovx: float, tanfo
         _check_render(L, L.rr_forward_geometry(ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs), _p(radii),
                                                _p(geom), geom.numel(), _p(img), img.numel(), ctypes.byref(nr),
                                                ctypes.byref(npairs), stream), "fused forward")
-    binning = torch.empty((L.rr_binning_bytes(npairs.value, W, H) if npairs.value > 0 else 0,), **u8)
+    nbin = L.rr_binning_bytes(npairs.value, W, H) if npairs.value > 0 else 0
+    binning = cache.get(nbin, dev) if cache is not None and nbin > 0 else torch.empty((nbin,), **u8)
     if P > 0:
-        _check_render(L, L.rr_forward_render(ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs), _p(radii),
-                                             _p(geom), _p(img), _p(binning), binning.numel(), npairs.value, _p(color),
-                                             _p(depth), stream), "fused forward")
+        _check_render(L, L.rr_forward_render_aux(ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs),
+                                                 _p(radii), _p(geom), _p(img), _p(binning), binning.numel(),
+                                                 npairs.value, _p(color), _p(depth), _p(nmap), stream),
+                      "fused forward")
     else:
         color.copy_(bg.view(3, 1, 1).expand(3, H, W))
         depth.zero_()
-    st = RawFrame(frame, cam, gs, (keep, params), radii, geom, img, binning, nr.value, P, M, ws)
+        if normal:
+            nmap.zero_()
+    st = RawFrame(frame, cam, gs, (keep, params), radii, geom, img, binning, nr.value, P, M, ws, nmap)
     return color, radii, depth, st
 
 
@@ -239,7 +250,8 @@ def forward_next(nxt: NextFrame, model, cache: BinningCache | None = None):
 
 def backward(st: RawFrame, dL_dpix: torch.Tensor, grads: dict | None, stats: tuple | None = None,
              adam: "N.RRAdam | None" = None, dmeans2D: torch.Tensor | None = None, next_frame: NextFrame | None = None,
-             dL_ddepth: torch.Tensor | None = None, dL_dalpha: torch.Tensor | None = None):
+             dL_ddepth: torch.Tensor | None = None, dL_dalpha: torch.Tensor | None = None,
+             dL_dnormal: torch.Tensor | None = None):
     """Write dLoss/d(raw parameter) into grads['xyz'|'f_dc'|'f_rest'|'opacity'|'scaling'|'rotation']
     (contiguous fp32 tensors of the parameter shapes, fully overwritten) and, if `stats` =
     (grad_accum [P,1], denom [P,1], max_radii2D [P]) is given, update the densification statistics
@@ -252,22 +264,26 @@ def backward(st: RawFrame, dL_dpix: torch.Tensor, grads: dict | None, stats: tup
     `dL_ddepth` / `dL_dalpha` ([1,H,W] or [H,W] fp32, optional): gradients of the depth map and of the
     accumulated alpha (accumulated_alpha()), added to the colour's in every output above, the
     statistics, the fused step and the next frame included (rr_backward_aux); `dL_dpix` may then
-    be None."""
+    be None.
+    `dL_dnormal` ([3,H,W] fp32, optional): gradient of the aux normal map of a frame rendered with
+    forward(normal=True), added likewise (rr_backward_aux_normal): it reaches the rotation directly
+    and everything else through alpha_i."""
     if st.P == 0:
         return
     L = N.raster()
-    aux = dL_ddepth is not None or dL_dalpha is not None
+    aux = dL_ddepth is not None or dL_dalpha is not None or dL_dnormal is not None
     if dL_dpix is None and not aux:
         raise RuntimeError("rain_amd.fused.backward: no output gradient given")
     npix = st.frame.width * st.frame.height
-    maps = []
-    for name, t in (("dL_ddepth", dL_ddepth), ("dL_dalpha", dL_dalpha)):
-        if t is not None:
-            if t.dtype != torch.float32 or t.numel() != npix:
-                raise RuntimeError(f"rain_amd.fused: {name} must be a float32 [1, H, W] tensor")
-            t = t.contiguous()
-        maps.append(t)
-    dpix = dL_dpix.contiguous() if dL_dpix is not None else maps[0] if maps[0] is not None else maps[1]
+    maps = [None, None, None]
+    if aux:
+        for i, (name, t, c) in enumerate((("dL_ddepth", dL_ddepth, 1), ("dL_dalpha", dL_dalpha, 1),
+                                          ("dL_dnormal", dL_dnormal, 3))):
+            if t is not None:
+                if t.dtype != torch.float32 or t.numel() != c * npix:
+                    raise RuntimeError(f"rain_amd.fused: {name} must be a float32 [{c}, H, W] tensor")
+                maps[i] = t.contiguous()
+    dpix = dL_dpix.contiguous() if dL_dpix is not None else next(m for m in maps if m is not None)
     names = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation")
     if grads is None:
         if adam is None:
@@ -291,6 +307,13 @@ def backward(st: RawFrame, dL_dpix: torch.Tensor, grads: dict | None, stats: tup
         frame.flags |= N.RR_FLAG_WORKSPACE_REGISTERED
     else:
         ws = torch.empty((L.rr_backward_workspace_bytes(st.P),), dtype=torch.uint8, device=dev)
+    if maps[2] is not None:
+        N.check(L.rr_backward_aux_normal(ctypes.byref(frame), ctypes.byref(st.cam), ctypes.byref(st.gs),
+                                         _p(st.radii), _p(st.geom), _p(st.img), _p(st.binning), st.num_rendered,
+                                         _p(dpix) if dL_dpix is not None else None, _p(maps[0]), _p(maps[1]),
+                                         _p(maps[2]), _p(ws), ws.numel(), ctypes.byref(out), N.stream_of(dpix)),
+                "fused backward (normal)")
+        return
     if aux:
         N.check(L.rr_backward_aux(ctypes.byref(frame), ctypes.byref(st.cam), ctypes.byref(st.gs), _p(st.radii),
                                   _p(st.geom), _p(st.img), _p(st.binning), st.num_rendered,
@@ -395,5 +418,46 @@ class RasterizeRawParamsDepth(torch.autograd.Function):
         if st.P == 0:
             d2.zero_()
         backward(st, grad_color, grads, dmeans2D=d2, dL_ddepth=grad_depth, dL_dalpha=grad_alpha)
+        return (grads["xyz"], grads["f_dc"], grads["f_rest"], grads["opacity"], grads["scaling"], grads["rotation"], d2,
+                None, None, None, None, None, None, None, None, None, None, None)
+
+
+class RasterizeRawParamsNormal(torch.autograd.Function):
+    """RasterizeRawParamsDepth plus a differentiable aux normal map (render(normal_grad=True)):
+    returns (color, radii, depth, alpha, normal) — normal = sum alpha_i T_i n_i [3,H,W] — and its
+    backward adds the normal's gradient to the others' (rr_backward_aux_normal)."""
+
+    @staticmethod
+    def forward(ctx, xyz, f_dc, f_rest, opacity, scaling, rotation, means2D, sh_degree, W, H, tanfovx, tanfovy,
+                viewmatrix, projmatrix, campos, bg, low_pass, scale_modifier):
+        color, radii, depth, st = forward_params((xyz, f_dc, f_rest, opacity, scaling, rotation), sh_degree, W, H,
+                                                 tanfovx, tanfovy, viewmatrix, projmatrix, campos, bg, low_pass,
+                                                 scale_modifier, normal=True)
+        alpha = accumulated_alpha(st)
+        keep, _p6 = st.keep
+        ctx.save_for_backward(xyz, f_dc, f_rest, opacity, scaling, rotation, st.radii, st.geom, st.img, st.binning,
+                              st.ws, *keep)
+        ctx.desc = (st.frame, st.cam, st.gs, st.num_rendered, st.P, st.M)
+        ctx.mark_non_differentiable(radii)
+        ctx.set_materialize_grads(False)
+        return color, radii, depth, alpha, st.normal
+
+    @staticmethod
+    def backward(ctx, grad_color, _grad_radii, grad_depth, grad_alpha, grad_normal):
+        if grad_color is None and grad_depth is None and grad_alpha is None and grad_normal is None:
+            return (None,) * 18
+        xyz, f_dc, f_rest, opacity, scaling, rotation, radii, geom, img, binning, ws, *keep = ctx.saved_tensors
+        frame, cam, gs, num_rendered, P, M = ctx.desc
+        p = (xyz, f_dc, opacity, scaling, rotation, f_rest)  # kernel order
+        ws_first = ws if not getattr(ctx, "ws_used", False) else None
+        ctx.ws_used = True
+        st = RawFrame(frame, cam, gs, (tuple(keep), p), radii, geom, img, binning, num_rendered, P, M, ws_first)
+        grads = dict(xyz=torch.empty_like(p[0]), f_dc=torch.empty_like(p[1]), opacity=torch.empty_like(p[2]),
+                     scaling=torch.empty_like(p[3]), rotation=torch.empty_like(p[4]), f_rest=torch.empty_like(p[5]))
+        d2 = torch.empty((st.P, 3), dtype=torch.float32, device=p[0].device)
+        if st.P == 0:
+            d2.zero_()
+        backward(st, grad_color, grads, dmeans2D=d2, dL_ddepth=grad_depth, dL_dalpha=grad_alpha,
+                 dL_dnormal=grad_normal)
         return (grads["xyz"], grads["f_dc"], grads["f_rest"], grads["opacity"], grads["scaling"], grads["rotation"], d2,
                 None, None, None, None, None, None, None, None, None, None, None)

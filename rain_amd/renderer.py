@@ -69,7 +69,13 @@ class PipelineParams:
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
-           low_pass=0.3, depth_grad=False):
+           low_pass=0.3, depth_grad=False, normal_grad=False):
+    """The reference's render(); `depth_grad` adds a differentiable "depth" and "alpha" to the
+    dictionary, `normal_grad` (which implies depth_grad) a differentiable aux "normal" map [3,H,W]
+    as well (sum alpha_i T_i n_i, GaussianRasterizer.forward_normal)."""
+    if normal_grad and pipe.compute_cov3D_python:
+        raise Exception("render(normal_grad=True) needs the scale/rotation pair (not compute_cov3D_python): "
+                        "normals come from the scale axes")
     xyz = pc.get_xyz
     raw = _raw_path_ok(pc, pipe, override_color)
     if raw:
@@ -93,12 +99,17 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         sh_degree=pc.active_sh_degree, campos=viewpoint_camera.camera_center, prefiltered=False, debug=pipe.debug,
         low_pass=low_pass)
     if raw:
-        from .fused import RasterizeRawParams, RasterizeRawParamsDepth
+        from .fused import RasterizeRawParams, RasterizeRawParamsDepth, RasterizeRawParamsNormal
 
         raw_args = (pc._xyz, pc._features_dc, pc._features_rest, pc._opacity, pc._scaling, pc._rotation,
                     screenspace_points, pc.active_sh_degree, raster_settings.image_width,
                     raster_settings.image_height, tanfovx, tanfovy, raster_settings.viewmatrix,
                     raster_settings.projmatrix, raster_settings.campos, bg_color, low_pass, scaling_modifier)
+        if normal_grad:
+            rendered_image, radii, depth, alpha, normal = RasterizeRawParamsNormal.apply(*raw_args)
+            return {"render": rendered_image, "viewspace_points": screenspace_points,
+                    "visibility_filter": radii > 0, "radii": radii, "depth": depth, "alpha": alpha,
+                    "normal": normal}
         if depth_grad:
             rendered_image, radii, depth, alpha = RasterizeRawParamsDepth.apply(*raw_args)
             return {"render": rendered_image, "viewspace_points": screenspace_points,
@@ -130,6 +141,12 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     else:
         colors_precomp = override_color
 
+    if normal_grad:
+        rendered_image, radii, depth, alpha, normal = rasterizer.forward_normal(
+            means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors_precomp, opacities=opacity,
+            scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp)
+        return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
+                "radii": radii, "depth": depth, "alpha": alpha, "normal": normal}
     if depth_grad:
         rendered_image, radii, depth, alpha = rasterizer.forward_depth(
             means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors_precomp, opacities=opacity,

@@ -27,7 +27,8 @@ from collections import Counter
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-KERNEL = "_ZN2rr11k_blend_bwdILb0EEEvNS_12BlendBwdArgsEPKfS3_"  # the default (colour-only) instantiation
+# the default (colour-only) instantiation
+KERNEL = "_ZN2rr11k_blend_bwdILi0EEEvNS_12BlendBwdArgsEPKfS3_S3_PK15HIP_vector_typeIfLj4EE"
 
 
 def opclass(op):
