@@ -26,7 +26,7 @@ CXXFLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-W
 LIBS = {
     "librain_raster.so": ["rr_forward.hip", "rr_bin.hip", "rr_blend_fwd_s.hip", "rr_blend.hip", "rr_backward.hip",
                           "rr_sort.hip", "rr_api.hip"],
-    "librain_loss.so": ["loss.hip"],
+    "librain_loss.so": ["loss.hip", "geom_loss.hip"],
     "librain_knn.so": ["knn.hip"],
     "librain_train.so": ["train.hip", "densify.hip"],
 }

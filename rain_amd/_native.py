@@ -200,7 +200,8 @@ def raster():
 
 LOSS_LIB = os.environ.get("RAIN_LOSS_LIB") or os.path.join(LIB_DIR, "librain_loss.so")
 LOSS_SYMBOLS = ["rl_workspace_bytes", "rl_l1_ssim_forward", "rl_l1_ssim_backward", "rl_l1_ssim_forward_backward",
-                "rl_last_error"]
+                "rl_last_error", "rl_geom_workspace_bytes", "rl_geom_forward", "rl_geom_backward",
+                "rl_geom_forward_backward"]
 _loss = None
 
 
@@ -219,6 +220,18 @@ def loss_lib():
         L.rl_l1_ssim_forward_backward.argtypes = [vp, vp, ci, ci, ci, cf, ctypes.POINTER(cf), vp, ctypes.c_size_t, vp,
                                                   vp, vp, vp, vp]
         L.rl_last_error.restype = ctypes.c_char_p
+        # geometry loss (rain_amd/csrc/geom_loss.hip): depth, alpha, normal, gt_depth, H, W, tanfovx, tanfovy,
+        # alpha_min, lambda_normal, lambda_depth, then the call's own tail
+        sz = ctypes.c_size_t
+        geom = [vp, vp, vp, vp, ci, ci, cf, cf, cf, cf, cf]
+        L.rl_geom_workspace_bytes.restype = sz
+        L.rl_geom_workspace_bytes.argtypes = [ci, ci]
+        L.rl_geom_forward.restype = ci
+        L.rl_geom_forward.argtypes = geom + [vp, sz, vp, vp, vp]
+        L.rl_geom_backward.restype = ci
+        L.rl_geom_backward.argtypes = geom + [vp, vp, vp, vp, vp, vp]
+        L.rl_geom_forward_backward.restype = ci
+        L.rl_geom_forward_backward.argtypes = geom + [vp, sz, vp, vp, vp, vp, vp, vp, vp]
         _loss = L
     return _loss
 

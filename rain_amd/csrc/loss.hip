@@ -20,6 +20,9 @@
 #include <string>
 
 #include "../../include/rain_loss.h"
+#include "loss_err.hpp"
+
+thread_local std::string rl_detail::g_err;  // rl_last_error()'s slot, shared with geom_loss.hip
 
 namespace {
 
@@ -55,7 +58,7 @@ constexpr int LA_BWD = RL_LA_BWD; // and backward (fewer live values: deeper que
 constexpr int NQ = 2;            // 64-column chunks per patch row
 constexpr int NB_MAX = 1 << 20;  // partial-sum slots
 
-thread_local std::string g_err;
+using rl_detail::g_err;
 
 struct Win {
     float w[11];

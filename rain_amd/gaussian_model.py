@@ -99,6 +99,10 @@ class OptimizationParams:
         self.densify_until_iter = 15_000
         self.densify_grad_threshold = 0.0002
         self.random_background = False
+        # opt-in (no reference counterpart): weight of the depth-normal consistency term
+        # (rain_amd.loss.fused_geometry_loss) added to the loss from `lambda_normal_from_iter` on
+        self.lambda_normal = 0.0
+        self.lambda_normal_from_iter = 7000
         for k, v in kw.items():
             setattr(self, k, v)
 

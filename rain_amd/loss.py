@@ -6,6 +6,10 @@ kernels (rain_amd/csrc/loss.hip) — the window is an outer product of the 1-D G
 (loss_utils.py:15-19), so it is applied as two 11-tap passes over an LDS tile.  ``ssim_separable``
 is the same factorisation in torch (a CPU-testable statement of what the kernel computes).  All are
 pinned to the reference's ssim values by tests/golden/loss.npz.
+
+``fused_geometry_loss`` (opt-in, no reference counterpart) is the depth-normal consistency + depth
+loss on the rasterizer's depth / alpha / normal maps (rain_amd/csrc/geom_loss.hip; definition in
+include/rain_loss.h), pinned to tests/geom_loss_ref.py.
 """
 from __future__ import annotations
 
@@ -139,6 +143,142 @@ def fused_l1_ssim_loss(img, gt, lambda_dssim=0.2):
     if img.dim() != 3 or img.device.type != "cuda":
         raise RuntimeError("fused_l1_ssim_loss expects a [C,H,W] tensor on a HIP device")
     return _FusedL1SSIM.apply(img, gt, lambda_dssim)
+
+
+def _geom_args(depth, alpha, normal, gt_depth, tanfovx, tanfovy, alpha_min, lambda_normal, lambda_depth):
+    """The maps made contiguous and the leading arguments every rl_geom_* call shares."""
+    if depth.device.type != "cuda":
+        raise RuntimeError("geometry loss: tensors must be on a HIP device (no CPU fallback)")
+    H, W = depth.shape[-2:]
+    maps = []
+    for name, t, c in (("depth", depth, 1), ("alpha", alpha, 1), ("normal", normal, 3), ("gt_depth", gt_depth, 1)):
+        if t is None:
+            maps.append(None)
+            continue
+        if t.dtype != torch.float32 or t.numel() != c * H * W or t.device != depth.device:
+            raise RuntimeError(f"geometry loss: {name} must be a float32 [{c}, {H}, {W}] tensor on the depth's device")
+        maps.append(t.contiguous())
+    ptr = [ctypes.c_void_p(t.data_ptr()) if t is not None else None for t in maps]
+    head = ptr + [H, W, float(tanfovx), float(tanfovy), float(alpha_min), float(lambda_normal), float(lambda_depth)]
+    return maps, head, H, W
+
+
+def geometry_loss_forward(depth, alpha, normal, tanfovx, tanfovy, lambda_normal, lambda_depth=0.0, gt_depth=None,
+                          alpha_min=0.1):
+    """Depth-normal consistency + depth loss, forward (include/rain_loss.h rl_geom_forward).  Returns
+    (loss scalar, parts [4] = {loss, L_n, L_d, valid pixels}, workspace for geometry_loss_backward)."""
+    from . import _native as N
+
+    L = N.loss_lib()
+    maps, head, H, W = _geom_args(depth, alpha, normal, gt_depth, tanfovx, tanfovy, alpha_min, lambda_normal,
+                                  lambda_depth)
+    dev = depth.device
+    ws = torch.empty((L.rl_geom_workspace_bytes(H, W),), dtype=torch.uint8, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    parts = torch.empty((4,), dtype=torch.float32, device=dev)
+    rc = L.rl_geom_forward(*head, ws.data_ptr(), ws.numel(), loss.data_ptr(), parts.data_ptr(), N.stream_of(depth))
+    if rc:
+        raise RuntimeError(L.rl_last_error().decode())
+    return loss, parts, ws
+
+
+def _geom_grad_buffers(depth, alpha, normal, out):
+    """(dD, dA, dN) to write: the caller's `out` triple or fresh uninitialised tensors."""
+    if out is not None:
+        return out
+    return (torch.empty_like(depth, memory_format=torch.contiguous_format),
+            torch.empty_like(alpha, memory_format=torch.contiguous_format),
+            torch.empty_like(normal, memory_format=torch.contiguous_format) if normal is not None else None)
+
+
+def geometry_loss_backward(depth, alpha, normal, tanfovx, tanfovy, lambda_normal, lambda_depth, gt_depth, alpha_min,
+                           ws, grad_loss=None, out=None):
+    """(dL/ddepth, dL/dalpha, dL/dnormal) scaled by grad_loss (a device scalar; None = 1); dnormal
+    is None without a normal map.  `out`: a (dD, dA, dN) triple of contiguous tensors to write into."""
+    from . import _native as N
+
+    L = N.loss_lib()
+    maps, head, H, W = _geom_args(depth, alpha, normal, gt_depth, tanfovx, tanfovy, alpha_min, lambda_normal,
+                                  lambda_depth)
+    dD, dA, dN = _geom_grad_buffers(maps[0], maps[1], maps[2], out)
+    if grad_loss is None:
+        grad_loss = _ones(depth.device)
+    g = grad_loss.reshape(1).contiguous().float()
+    rc = L.rl_geom_backward(*head, ws.data_ptr(), g.data_ptr(), dD.data_ptr(), dA.data_ptr(),
+                            dN.data_ptr() if dN is not None else None, N.stream_of(depth))
+    if rc:
+        raise RuntimeError(L.rl_last_error().decode())
+    return dD, dA, dN
+
+
+def geometry_loss_forward_backward(depth, alpha, normal, tanfovx, tanfovy, lambda_normal, lambda_depth=0.0,
+                                   gt_depth=None, alpha_min=0.1, grad_loss=None, out=None):
+    """Forward and backward at once (the training step's form): (loss, parts, dD, dA, dN), bitwise
+    geometry_loss_forward's loss / parts and geometry_loss_backward's gradients, in two launches."""
+    from . import _native as N
+
+    L = N.loss_lib()
+    maps, head, H, W = _geom_args(depth, alpha, normal, gt_depth, tanfovx, tanfovy, alpha_min, lambda_normal,
+                                  lambda_depth)
+    dev = depth.device
+    ws = torch.empty((L.rl_geom_workspace_bytes(H, W),), dtype=torch.uint8, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    parts = torch.empty((4,), dtype=torch.float32, device=dev)
+    dD, dA, dN = _geom_grad_buffers(maps[0], maps[1], maps[2], out)
+    if grad_loss is None:
+        grad_loss = _ones(dev)
+    g = grad_loss.reshape(1).contiguous().float()
+    rc = L.rl_geom_forward_backward(*head, ws.data_ptr(), ws.numel(), loss.data_ptr(), parts.data_ptr(), g.data_ptr(),
+                                    dD.data_ptr(), dA.data_ptr(), dN.data_ptr() if dN is not None else None,
+                                    N.stream_of(depth))
+    if rc:
+        raise RuntimeError(L.rl_last_error().decode())
+    return loss, parts, dD, dA, dN
+
+
+class _FusedGeometryLoss(torch.autograd.Function):
+    """lambda_normal·L_n + lambda_depth·L_d in two HIP kernels (rain_amd/csrc/geom_loss.hip)."""
+
+    @staticmethod
+    def forward(ctx, depth, alpha, normal, gt_depth, tanfovx, tanfovy, lambda_normal, lambda_depth, alpha_min):
+        depth = depth.contiguous()
+        alpha = alpha.contiguous()
+        normal = normal.contiguous() if normal is not None else None
+        gt_depth = gt_depth.contiguous() if gt_depth is not None else None
+        ctx.cfg = (float(tanfovx), float(tanfovy), float(lambda_normal), float(lambda_depth), float(alpha_min))
+        loss, parts, ws = geometry_loss_forward(depth, alpha, normal, ctx.cfg[0], ctx.cfg[1], ctx.cfg[2], ctx.cfg[3],
+                                                gt_depth, ctx.cfg[4])
+        ctx.has = (normal is not None, gt_depth is not None)
+        ctx.save_for_backward(*[t for t in (depth, alpha, normal, gt_depth, ws) if t is not None])
+        ctx.mark_non_differentiable(parts)
+        ctx.set_materialize_grads(False)
+        return loss, parts
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_parts):
+        if grad_loss is None:  # the loss itself not in the differentiated graph
+            return (None,) * 9
+        saved = list(ctx.saved_tensors)
+        depth, alpha = saved[0], saved[1]
+        normal = saved[2] if ctx.has[0] else None
+        gt_depth = saved[2 + ctx.has[0]] if ctx.has[1] else None
+        ws = saved[-1]
+        tx, ty, ln, ld, amin = ctx.cfg
+        dD, dA, dN = geometry_loss_backward(depth, alpha, normal, tx, ty, ln, ld, gt_depth, amin, ws, grad_loss)
+        return (dD, dA, dN) + (None,) * 6
+
+
+def fused_geometry_loss(depth, alpha, normal, tanfovx, tanfovy, lambda_normal=0.05, lambda_depth=0.0, gt_depth=None,
+                        alpha_min=0.1):
+    """Depth-normal consistency (2DGS / GOF / PGSR style) with an optional metric depth prior, on
+    the maps render(normal_grad=True) returns: depth [1,H,W] = Σ α T z, alpha [1,H,W] = Σ α T, normal
+    [3,H,W] = Σ α T n (include/rain_loss.h has the definition).  Returns (loss, parts) with parts =
+    [loss, L_n, L_d, valid pixels] (device, no sync, not differentiable); gradients reach depth,
+    alpha and normal.  `normal` may be None with lambda_normal = 0."""
+    if depth.dim() != 3 or depth.device.type != "cuda":
+        raise RuntimeError("fused_geometry_loss expects [1,H,W] / [3,H,W] tensors on a HIP device")
+    return _FusedGeometryLoss.apply(depth, alpha, normal, gt_depth, tanfovx, tanfovy, lambda_normal, lambda_depth,
+                                    alpha_min)
 
 
 @lru_cache(maxsize=8)

@@ -29,7 +29,7 @@ import torch
 import torch.distributed as dist
 
 from .gaussian_model import GaussianModel, OptimizationParams, low_pass_schedule
-from .loss import fused_l1_ssim_loss
+from .loss import fused_geometry_loss, fused_l1_ssim_loss
 from .optim import sharded_adam_step
 from .renderer import PipelineParams, render
 
@@ -234,6 +234,7 @@ class Trainer:
             self._owner = ShardedStep(self.exchange, self.rank, self.world)
         if self.fused and not (dev.type == "cuda" and loss_fn is None and plain_pipe):
             raise ValueError("fused step needs a HIP device, the default loss and the default pipeline")
+        self._geometry_weight(0)  # a non-zero lambda_normal on the sharded paths is refused here already
 
     def _low_pass_and_view(self, iteration):
         g, opt, cfg = self.g, self.opt, self.cfg
@@ -302,6 +303,18 @@ class Trainer:
             g.optimizer.zero_grad(set_to_none=True)
         return densified
 
+    def _geometry_weight(self, iteration: int) -> float:
+        """The weight of the depth-normal consistency term at `iteration`: OptimizationParams.lambda_normal
+        from lambda_normal_from_iter on, else 0 (today's step, untouched)."""
+        lam = float(getattr(self.opt, "lambda_normal", 0.0) or 0.0)
+        if lam <= 0.0:
+            return 0.0
+        if self.sharded:
+            raise ValueError("lambda_normal > 0 needs the single-GPU step: the Gaussian-sharded / multi-rank steps "
+                             "have no normal-map backward (k_gauss_bwd_views has no normal variant); train on one "
+                             "GPU or set lambda_normal = 0")
+        return lam if iteration >= int(getattr(self.opt, "lambda_normal_from_iter", 0)) else 0.0
+
     def step(self, iteration: int, sync_loss: bool = False) -> StepInfo:
         if self.fused:
             return self._step_fused(iteration, sync_loss)
@@ -364,8 +377,9 @@ class Trainer:
 
     def _step_fused(self, iteration: int, sync_loss: bool) -> StepInfo:
         from . import fused
-        from .loss import l1_ssim_forward_backward
+        from .loss import geometry_loss_forward_backward, l1_ssim_forward_backward
 
+        lam_n = self._geometry_weight(iteration)  # refuses the sharded steps when the weight is set
         if self._owner is not None:
             return self._step_owner(iteration, sync_loss)
 
@@ -378,6 +392,8 @@ class Trainer:
             if nxt is not None and (nxt.P != g.get_xyz.shape[0] or nxt.frame.D != g.active_sh_degree
                                     or sig != self._params_signature()):
                 nxt = None  # the parameters changed since step s-1's backward preprocessed this frame
+            if lam_n:
+                nxt = None  # a frame with the aux normal map runs its own preprocess
         else:
             vidx, cam = self._low_pass_and_view(iteration)
             nxt = None
@@ -408,7 +424,7 @@ class Trainer:
         # inside that backward (no densify / reset replacing parameters) and the SH degree stays
         next_frame = None
         if (fuse_adam and self.fuse_next and not self.sharded and iteration + 1 < opt.iterations
-                and not self._sh_steps_up(iteration + 1)):
+                and not self._sh_steps_up(iteration + 1) and not lam_n and not self._geometry_weight(iteration + 1)):
             low_pass_now = self.low_pass
             vidx1, cam1 = self._low_pass_and_view(iteration + 1)
             next_frame = fused.prepare_next(g, cam1, self.background, self.low_pass)
@@ -419,10 +435,20 @@ class Trainer:
             if nxt is not None:
                 image, radii, _depth, st = fused.forward_next(nxt, g, cache=cache)
             else:
-                image, radii, _depth, st = fused.forward(g, cam, self.background, self.low_pass, cache=cache)
+                image, radii, _depth, st = fused.forward(g, cam, self.background, self.low_pass, cache=cache,
+                                                         normal=bool(lam_n))
             # loss and dL/dimage in one call (bitwise the separate forward / backward)
             loss, _parts, dimg = l1_ssim_forward_backward(image, gt, opt.lambda_dssim)
-            fused.backward(st, dimg, grads, stats, adam=adam, next_frame=next_frame)
+            if lam_n:
+                # depth-normal consistency on the frame's depth / alpha / normal maps: two more launches,
+                # its three map gradients join the colour's in the one backward
+                gloss, _gparts, dD, dA, dN = geometry_loss_forward_backward(
+                    _depth, fused.accumulated_alpha(st), st.normal, st.frame.tan_fovx, st.frame.tan_fovy, lam_n)
+                fused.backward(st, dimg, grads, stats, adam=adam, dL_ddepth=dD, dL_dalpha=dA, dL_dnormal=dN)
+                if sync_loss:
+                    loss = loss + gloss
+            else:
+                fused.backward(st, dimg, grads, stats, adam=adam, next_frame=next_frame)
             densified = self._finish(iteration, flat, densify_now, reset_now, adam_done=fuse_adam)
         if self._pending is not None:  # the parameters the pending geometry was computed from
             self._pending[5] = self._params_signature()
@@ -489,6 +515,7 @@ class Trainer:
     def _step_autograd(self, iteration: int, sync_loss: bool = False) -> StepInfo:
         """The reference-API step: render() through GaussianRasterizer + autograd (train.py:109-147)."""
         g, opt = self.g, self.opt
+        lam_n = self._geometry_weight(iteration)
         vidx, cam = self._low_pass_and_view(iteration)
         densify_phase = iteration < opt.densify_until_iter
         densify_now, reset_now = self._events(iteration)
@@ -500,11 +527,15 @@ class Trainer:
             for p in g.params():
                 p.grad = None
 
-        pkg = render(cam, g, self.pipe, self.background, low_pass=self.low_pass)
+        pkg = render(cam, g, self.pipe, self.background, low_pass=self.low_pass, normal_grad=bool(lam_n))
         image, vsp, vis, radii = pkg["render"], pkg["viewspace_points"], pkg["visibility_filter"], pkg["radii"]
         gt = self.gt[vidx]
         # (1-λ)·L1 + λ·(1-SSIM) (train.py:113-114), by default one fused HIP forward/backward
         loss = self.loss_fn(image, gt, opt.lambda_dssim)
+        if lam_n:  # + lambda_normal · depth-normal consistency (rain_amd/csrc/geom_loss.hip)
+            loss = loss + fused_geometry_loss(pkg["depth"], pkg["alpha"], pkg["normal"],
+                                              math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5),
+                                              lambda_normal=lam_n)[0]
         loss.backward()
 
         with torch.no_grad():
