@@ -81,6 +81,34 @@ int rl_geom_forward_backward(const float* depth, const float* alpha, const float
                              float lambda_depth, void* workspace, size_t workspace_bytes, float* loss, float* parts,
                              const float* grad_loss, float* d_depth, float* d_alpha, float* d_normal, void* stream);
 
+/*
+ * Depth-distortion loss on the rasterizer's accumulated alpha A [H,W] and depth-moment maps
+ * moments [2,H,W] = (M1, M2) (include/rain_raster.h rr_forward_render_dist):
+ *   L = lambda_dist * (1/HW) sum_p (A M2 - M1^2)                       (no clamp)
+ *   dL/dA = lambda_dist/HW M2,  dL/dM1 = -2 lambda_dist/HW M1,  dL/dM2 = lambda_dist/HW A.
+ * loss[0] = L; parts (device, optional) = {L, the unweighted mean}.  Deterministic like rl_geom_*:
+ * per-block partial sums in double reduced in a fixed order, no atomics, no host synchronisation.
+ * Return codes as rl_geom_* (1 bad argument, 2 HIP error, 3 workspace too small).
+ */
+size_t rl_dist_workspace_bytes(int H, int W); /* the block partials */
+
+int rl_dist_forward(const float* alpha, const float* moments, int H, int W, float lambda_dist, void* workspace,
+                    size_t workspace_bytes, float* loss, float* parts, void* stream);
+
+/* d_alpha [H,W], d_moments [2,H,W] = grad_loss[0] * dL/d(map) (grad_loss: device scalar).  d_moments is
+ * overwritten.  accumulate_alpha != 0: the alpha gradient is ADDED to what d_alpha holds (one rounded
+ * product, one add per pixel), so that rl_geom_*'s alpha gradient and this one combine without another
+ * launch; 0: d_alpha is overwritten.  Needs no workspace. */
+int rl_dist_backward(const float* alpha, const float* moments, int H, int W, float lambda_dist,
+                     const float* grad_loss, float* d_alpha, float* d_moments, int accumulate_alpha, void* stream);
+
+/* Both at once in two launches (the loss finalize rides on the second): loss / parts bitwise
+ * rl_dist_forward's, the gradients bitwise rl_dist_backward's. */
+int rl_dist_forward_backward(const float* alpha, const float* moments, int H, int W, float lambda_dist,
+                             void* workspace, size_t workspace_bytes, float* loss, float* parts,
+                             const float* grad_loss, float* d_alpha, float* d_moments, int accumulate_alpha,
+                             void* stream);
+
 const char* rl_last_error(void);
 
 #ifdef __cplusplus

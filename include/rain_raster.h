@@ -289,6 +289,49 @@ int rr_backward_aux_normal(const rr_frame* f, const rr_camera* cam, const rr_gau
                            const float* dL_dnormal, void* workspace, size_t workspace_bytes, const rr_grads* out,
                            void* stream);
 
+/*
+ * Depth-moment maps for the depth-distortion loss (opt-in).  With w_i = alpha_i T_i and m_i = m(z_i)
+ * a mapped view depth, the renderer blends M1(p) = sum_i w_i m_i and M2(p) = sum_i w_i m_i^2 (no
+ * background term), from which the caller forms the distortion
+ *   sum_{i>j} w_i w_j (m_i - m_j)^2 = A M2 - M1^2        (A = sum_i w_i, rr_render_alpha).
+ * The mapping is chosen by (dist_near, dist_far):
+ *   0 < near < far:         m(z) = far / (far - near) * (1 - near / z)   (NDC depth),
+ *                           dm/dz = far near / ((far - near) z^2);
+ *   near == 0 && far == 0:  m(z) = z, dm/dz = 1                          (metric scenes).
+ * Any other pair is RR_ERR_ARG before any device work.  m is formed once per (tile, Gaussian) pair
+ * from the splat record's depth; preprocess, splat records and the geometry buffer are unchanged.
+ *
+ * rr_forward_render_dist: rr_forward_render_aux plus out_moments [2,H,W] (planes M1, M2; required).
+ * out_normal follows rr_forward_render_aux's rule (given exactly when RR_FLAG_AUX_NORMAL is set).
+ * Colour, depth, normal, radii and the buffers are bitwise those of rr_forward_render_aux.
+ */
+int rr_forward_render_dist(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
+                           void* geom_buffer, void* image_buffer, void* binning_buffer, size_t binning_bytes,
+                           int num_pairs, float* out_color, float* out_depth, float* out_normal, float* out_moments,
+                           float dist_near, float dist_far, void* stream);
+
+/*
+ * rr_backward_aux_normal plus a gradient of the depth-moment maps: dL_dmoments is [2,H,W] planar
+ * (dL/dM1, dL/dM2) or NULL, dist_near / dist_far the mapping the frame was rendered with.  With
+ * dL_dmoments == NULL this is exactly rr_backward_aux_normal (the same dispatch and kernels;
+ * dist_near / dist_far are then not looked at).  Otherwise dL_dpix, dL_ddepth, dL_dalpha and dL_dnormal
+ * may each be NULL (zero), and:
+ *   - dL/dalpha_i gains m_i dL/dM1(p) + m_i^2 dL/dM2(p), so opacity, position and covariance see the
+ *     moment term like the colour term (no mask for the 0.99 alpha clamp);
+ *   - dL/dz_i gains sum_p alpha_i T_i dm/dz (dL/dM1 + 2 m_i dL/dM2), which reaches dL/dmeans3D through
+ *     the view matrix's z row like the depth map's term;
+ *   - a bad (dist_near, dist_far) pair is RR_ERR_ARG before any device work; the rules for dL_dnormal
+ *     (RR_FLAG_AUX_NORMAL, scales / rotations) are rr_backward_aux_normal's, and moments without a
+ *     normal gradient accept cov3D_precomp.
+ * rr_grads.adam, the densification statistics, rr_grads.next (a frame without aux flags) and
+ * RR_FLAG_WORKSPACE_REGISTERED behave as in rr_backward_aux_normal.
+ */
+int rr_backward_aux_dist(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
+                         const void* geom_buffer, const void* image_buffer, const void* binning_buffer,
+                         int num_rendered, const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha,
+                         const float* dL_dnormal, const float* dL_dmoments, float dist_near, float dist_far,
+                         void* workspace, size_t workspace_bytes, const rr_grads* out, void* stream);
+
 /* out_alpha [H*W] = 1 - T_final of the frame last rendered into image_buffer (f: that frame). */
 int rr_render_alpha(const rr_frame* f, const void* image_buffer, float* out_alpha, void* stream);
 

@@ -101,7 +101,8 @@ RASTER_SYMBOLS = ["rr_geometry_bytes", "rr_image_bytes", "rr_binning_bytes", "rr
                   "rr_preprocess_rows", "rr_preprocess_rows_views", "rr_unpack_rows", "rr_forward_from_geometry",
                   "rr_forward_render_geometry",
                   "rr_backward_records", "rr_gauss_backward_views", "rr_set_forward_workspace",
-                  "rr_backward_aux", "rr_render_alpha", "rr_backward_aux_normal"]
+                  "rr_backward_aux", "rr_render_alpha", "rr_backward_aux_normal",
+                  "rr_forward_render_dist", "rr_backward_aux_dist"]
 
 _raster = None
 _knn = None
@@ -146,6 +147,14 @@ def raster():
         L.rr_backward_aux_normal.restype = ci
         L.rr_backward_aux_normal.argtypes = [fp, cp, gp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, sz,
                                              ctypes.POINTER(RRGrads), vp]
+        # rr_forward_render_aux plus out_moments, dist_near, dist_far before the stream
+        cf = ctypes.c_float
+        L.rr_forward_render_dist.restype = ci
+        L.rr_forward_render_dist.argtypes = [fp, cp, gp, vp, vp, vp, vp, sz, ci, vp, vp, vp, vp, cf, cf, vp]
+        # rr_backward_aux_normal plus dL_dmoments, dist_near, dist_far after dL_dnormal
+        L.rr_backward_aux_dist.restype = ci
+        L.rr_backward_aux_dist.argtypes = [fp, cp, gp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, cf, cf, vp, sz,
+                                           ctypes.POINTER(RRGrads), vp]
         L.rr_render_alpha.restype = ci
         L.rr_render_alpha.argtypes = [fp, vp, vp, vp]
         L.rr_mark_visible.restype = ci
@@ -201,7 +210,8 @@ def raster():
 LOSS_LIB = os.environ.get("RAIN_LOSS_LIB") or os.path.join(LIB_DIR, "librain_loss.so")
 LOSS_SYMBOLS = ["rl_workspace_bytes", "rl_l1_ssim_forward", "rl_l1_ssim_backward", "rl_l1_ssim_forward_backward",
                 "rl_last_error", "rl_geom_workspace_bytes", "rl_geom_forward", "rl_geom_backward",
-                "rl_geom_forward_backward"]
+                "rl_geom_forward_backward", "rl_dist_workspace_bytes", "rl_dist_forward", "rl_dist_backward",
+                "rl_dist_forward_backward"]
 _loss = None
 
 
@@ -232,6 +242,16 @@ def loss_lib():
         L.rl_geom_backward.argtypes = geom + [vp, vp, vp, vp, vp, vp]
         L.rl_geom_forward_backward.restype = ci
         L.rl_geom_forward_backward.argtypes = geom + [vp, sz, vp, vp, vp, vp, vp, vp, vp]
+        # distortion loss (geom_loss.hip rl_dist_*): alpha, moments, H, W, lambda_dist, then the call's own tail
+        dist = [vp, vp, ci, ci, cf]
+        L.rl_dist_workspace_bytes.restype = sz
+        L.rl_dist_workspace_bytes.argtypes = [ci, ci]
+        L.rl_dist_forward.restype = ci
+        L.rl_dist_forward.argtypes = dist + [vp, sz, vp, vp, vp]
+        L.rl_dist_backward.restype = ci
+        L.rl_dist_backward.argtypes = dist + [vp, vp, vp, ci, vp]
+        L.rl_dist_forward_backward.restype = ci
+        L.rl_dist_forward_backward.argtypes = dist + [vp, sz, vp, vp, vp, vp, vp, ci, vp]
         _loss = L
     return _loss
 

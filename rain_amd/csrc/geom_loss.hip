@@ -498,3 +498,234 @@ int rl_geom_forward_backward(const float* depth, const float* alpha, const float
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// Depth-distortion loss (include/rain_loss.h, rl_dist_*): with the rasterizer's accumulated alpha A
+// and depth-moment maps M1 = sum w m, M2 = sum w m^2 (include/rain_raster.h rr_forward_render_dist),
+//   L = lambda (1/HW) sum_p (A M2 - M1^2)       (= sum_{i>j} w_i w_j (m_i - m_j)^2 per pixel; no clamp)
+//   dL/dA = lambda/HW M2,  dL/dM1 = -2 lambda/HW M1,  dL/dM2 = lambda/HW A.
+// Pointwise: the maps are walked as flat arrays of HW pixels, V = 4 per thread when HW is a multiple
+// of 4 and every pointer is 16-byte aligned (the M2 plane then is too), else V = 1.  Loss sum: per-block
+// partials in double, reduced in a fixed order by one block (its own launch after the forward, or
+// the extra block of the backward launch: the same additions in the same order).  No atomics.
+namespace {
+
+constexpr int kDistNbMax = 1 << 20;
+
+struct DistP {
+    const float* A;
+    const float* M;  // [2,HW]
+    size_t n;        // HW
+    float lam, k;    // lambda, lambda / HW
+    double inv_n;
+};
+
+__device__ __forceinline__ double block_sum1(double s) {
+    __shared__ double sm1[kThreads / 64];
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if ((tid & 63) == 0) sm1[tid >> 6] = s;
+    __syncthreads();
+    double t = 0.0;
+    if (tid == 0)
+        for (int w = 0; w < kThreads / 64; w++) t += sm1[w];
+    return t;  // thread 0's value is the block's sum
+}
+
+__device__ __forceinline__ void dist_finalize(const double* __restrict__ partial, int nb, const DistP& g,
+                                              float* __restrict__ loss, float* __restrict__ parts) {
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nb; i += kThreads) s += partial[i];
+    const double t = block_sum1(s);
+    if (threadIdx.x == 0) {
+        const float mean = (float)(t * g.inv_n);
+        const float total = g.lam * mean;
+        loss[0] = total;
+        if (parts) {
+            parts[0] = total;
+            parts[1] = mean;
+        }
+    }
+}
+
+template <int V>
+__global__ __launch_bounds__(kThreads) void k_dist_fwd(DistP g, double* __restrict__ partial) {
+    const size_t i = ((size_t)blockIdx.x * kThreads + threadIdx.x) * V;
+    double s = 0.0;
+    if (i < g.n) {  // V == 4: n is a multiple of 4, so i + 3 < n
+        float a[V], m1[V], m2[V];
+        load_v<V>(g.A, i, a);
+        load_v<V>(g.M, i, m1);
+        load_v<V>(g.M + g.n, i, m2);
+#pragma unroll
+        for (int k = 0; k < V; k++) s += (double)(a[k] * m2[k] - m1[k] * m1[k]);
+    }
+    const double t = block_sum1(s);
+    if (threadIdx.x == 0) partial[blockIdx.x] = t;
+}
+
+__global__ __launch_bounds__(kThreads) void k_dist_finalize(DistP g, const double* __restrict__ partial, int nb,
+                                                            float* __restrict__ loss, float* __restrict__ parts) {
+    dist_finalize(partial, nb, g, loss, parts);
+}
+
+template <int V>
+__global__ __launch_bounds__(kThreads) void k_dist_bwd(DistP g, const float* __restrict__ grad_loss,
+                                                       float* __restrict__ dA, float* __restrict__ dM, int accumulate,
+                                                       const double* __restrict__ partial, int nb,
+                                                       float* __restrict__ loss, float* __restrict__ parts) {
+#pragma clang fp contract(off)  // the accumulated alpha gradient is old + (c M2), never fma(c, M2, old)
+    if (loss && blockIdx.x == gridDim.x - 1) {  // the extra block (block-uniform): the forward's finalize
+        dist_finalize(partial, nb, g, loss, parts);
+        return;
+    }
+    const size_t i = ((size_t)blockIdx.x * kThreads + threadIdx.x) * V;
+    if (i >= g.n) return;
+    const float c = grad_loss[0] * g.k;
+    float a[V], m1[V], m2[V], oa[V], o1[V], o2[V];
+    load_v<V>(g.A, i, a);
+    load_v<V>(g.M, i, m1);
+    load_v<V>(g.M + g.n, i, m2);
+    if (accumulate) load_v<V>(dA, i, oa);
+#pragma unroll
+    for (int k = 0; k < V; k++) {
+        const float ga = c * m2[k];
+        oa[k] = accumulate ? oa[k] + ga : ga;  // a plain add of the rounded gradient
+        o1[k] = -2.f * c * m1[k];
+        o2[k] = c * a[k];
+    }
+    store_v<V>(dA, i, oa);
+    store_v<V>(dM, i, o1);
+    store_v<V>(dM + g.n, i, o2);
+}
+
+inline int dist_blocks(size_t n, int V) { return (int)((n + (size_t)kThreads * V - 1) / ((size_t)kThreads * V)); }
+
+int dist_validate(const char* who, const float* A, const float* M, int H, int W) {
+    if (H <= 0 || W <= 0) {
+        g_err = std::string(who) + ": bad argument (H and W must be positive)";
+        return 1;
+    }
+    if (!A || !M) {
+        g_err = std::string(who) + ": bad argument (null alpha or moments)";
+        return 1;
+    }
+    if ((size_t)H * W >= ((size_t)1 << 28)) {
+        g_err = std::string(who) + ": image larger than 2^28 pixels";
+        return 1;
+    }
+    return 0;
+}
+
+DistP dist_params(const float* A, const float* M, int H, int W, float lam) {
+    DistP g;
+    g.A = A;
+    g.M = M;
+    g.n = (size_t)H * W;
+    g.lam = lam;
+    g.k = (float)((double)lam / (double)g.n);
+    g.inv_n = 1.0 / (double)g.n;
+    return g;
+}
+
+int dist_pick_v(const DistP& g, const float* dA, const float* dM) {
+    return (g.n % 4 == 0 && aligned16(g.A) && aligned16(g.M) && aligned16(dA) && aligned16(dM)) ? 4 : 1;
+}
+
+void dist_launch_fwd(const DistP& g, int V, double* partial, hipStream_t st) {
+    if (V == 4)
+        k_dist_fwd<4><<<dist_blocks(g.n, 4), kThreads, 0, st>>>(g, partial);
+    else
+        k_dist_fwd<1><<<dist_blocks(g.n, 1), kThreads, 0, st>>>(g, partial);
+}
+
+void dist_launch_bwd(const DistP& g, int V, const float* grad_loss, float* dA, float* dM, int accumulate,
+                     const double* partial, float* loss, float* parts, hipStream_t st) {
+    const int nb = dist_blocks(g.n, V);
+    const int grid = nb + (loss ? 1 : 0);
+    if (V == 4)
+        k_dist_bwd<4><<<grid, kThreads, 0, st>>>(g, grad_loss, dA, dM, accumulate, partial, nb, loss, parts);
+    else
+        k_dist_bwd<1><<<grid, kThreads, 0, st>>>(g, grad_loss, dA, dM, accumulate, partial, nb, loss, parts);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t rl_dist_workspace_bytes(int H, int W) {
+    if (H <= 0 || W <= 0) return 0;
+    return (size_t)dist_blocks((size_t)H * W, 1) * sizeof(double) + 256;  // the V = 1 form's block count
+}
+
+int rl_dist_forward(const float* alpha, const float* moments, int H, int W, float lambda_dist, void* workspace,
+                    size_t workspace_bytes, float* loss, float* parts, void* stream) {
+    const char* who = "rl_dist_forward";
+    if (int rc = dist_validate(who, alpha, moments, H, W)) return rc;
+    if (!workspace || !loss) {
+        g_err = std::string(who) + ": bad argument (null workspace or loss)";
+        return 1;
+    }
+    if (workspace_bytes < rl_dist_workspace_bytes(H, W)) {
+        g_err = std::string(who) + ": workspace too small";
+        return 3;
+    }
+    const DistP g = dist_params(alpha, moments, H, W, lambda_dist);
+    double* partial = static_cast<double*>(workspace);
+    hipStream_t st = (hipStream_t)stream;
+    const int V = dist_pick_v(g, nullptr, nullptr);
+    dist_launch_fwd(g, V, partial, st);
+    k_dist_finalize<<<1, kThreads, 0, st>>>(g, partial, dist_blocks(g.n, V), loss, parts);
+    return launch_status(who);
+}
+
+int rl_dist_backward(const float* alpha, const float* moments, int H, int W, float lambda_dist,
+                     const float* grad_loss, float* d_alpha, float* d_moments, int accumulate_alpha, void* stream) {
+    const char* who = "rl_dist_backward";
+    if (int rc = dist_validate(who, alpha, moments, H, W)) return rc;
+    if (!grad_loss || !d_alpha || !d_moments) {
+        g_err = std::string(who) + ": bad argument (null grad_loss or gradient output)";
+        return 1;
+    }
+    const DistP g = dist_params(alpha, moments, H, W, lambda_dist);
+    const int V = dist_pick_v(g, d_alpha, d_moments);
+    dist_launch_bwd(g, V, grad_loss, d_alpha, d_moments, accumulate_alpha, nullptr, nullptr, nullptr,
+                    (hipStream_t)stream);
+    return launch_status(who);
+}
+
+int rl_dist_forward_backward(const float* alpha, const float* moments, int H, int W, float lambda_dist,
+                             void* workspace, size_t workspace_bytes, float* loss, float* parts,
+                             const float* grad_loss, float* d_alpha, float* d_moments, int accumulate_alpha,
+                             void* stream) {
+    const char* who = "rl_dist_forward_backward";
+    if (int rc = dist_validate(who, alpha, moments, H, W)) return rc;
+    if (!workspace || !loss || !grad_loss || !d_alpha || !d_moments) {
+        g_err = std::string(who) + ": bad argument (null workspace, loss, grad_loss or gradient output)";
+        return 1;
+    }
+    if (workspace_bytes < rl_dist_workspace_bytes(H, W)) {
+        g_err = std::string(who) + ": workspace too small";
+        return 3;
+    }
+    const DistP g = dist_params(alpha, moments, H, W, lambda_dist);
+    double* partial = static_cast<double*>(workspace);
+    hipStream_t st = (hipStream_t)stream;
+    // the forward's vector width: the loss is then bitwise rl_dist_forward's whatever the gradient
+    // outputs' alignment
+    const int Vf = dist_pick_v(g, nullptr, nullptr);
+    dist_launch_fwd(g, Vf, partial, st);
+    const int nbf = dist_blocks(g.n, Vf);
+    const int V = dist_pick_v(g, d_alpha, d_moments);
+    const int nb = dist_blocks(g.n, V);
+    if (V == 4)
+        k_dist_bwd<4><<<nb + 1, kThreads, 0, st>>>(g, grad_loss, d_alpha, d_moments, accumulate_alpha, partial, nbf, loss,
+                                                   parts);
+    else
+        k_dist_bwd<1><<<nb + 1, kThreads, 0, st>>>(g, grad_loss, d_alpha, d_moments, accumulate_alpha, partial, nbf, loss,
+                                                   parts);
+    return launch_status(who);
+}
+
+}  // extern "C"

@@ -472,7 +472,7 @@ int windowed_phase(const rr_frame* f, const Geom& gm, const Bin& bn, DupArgs<K>&
 // count on the device (FrameTotals LA / LB, or the gather path's counters).
 template <typename K>
 int render_tiles(const rr_frame* f, const Geom& gm, const Img& im, const Bin& bn, const int* radii, int P, int W,
-                 int H, int cull, bool early, BlendFwdArgs b, hipStream_t st) {
+                 int H, int cull, bool early, BlendFwdArgs b, const DistFwdArgs& dm, hipStream_t st) {
     const int gx = grid_x(W), gy = grid_y(H);
     const uint32_t L = bn.L;
     DupArgs<K> d{};
@@ -498,7 +498,7 @@ int render_tiles(const rr_frame* f, const Geom& gm, const Img& im, const Bin& bn
     if (int rc = windowed_phase<K>(f, gm, bn, d, wa, st, &starts_b)) return rc;
     b.phase = early ? kBlendPhaseA : kBlendSingle;
     // (clears the registered backward workspace, render_frame, in its drain)
-    if (int rc = stage(f, st, RR_STAGE_BLEND_FWD, "blend forward", [&] { launch_blend_fwd(b, st); })) return rc;
+    if (int rc = stage(f, st, RR_STAGE_BLEND_FWD, "blend forward", [&] { launch_blend_fwd(b, st, &dm); })) return rc;
     b.clear = nullptr;
     b.clear_n4 = 0;
     if (!early) return RR_OK;
@@ -530,13 +530,13 @@ int render_tiles(const rr_frame* f, const Geom& gm, const Img& im, const Bin& bn
         if (int rc = windowed_phase<K>(f, gm, bn, d, wb, st, &starts)) return rc;
     }
     b.phase = kBlendPhaseB;
-    return stage(f, st, RR_STAGE_BLEND_FWD, "blend forward (phase B)", [&] { launch_blend_fwd(b, st); });
+    return stage(f, st, RR_STAGE_BLEND_FWD, "blend forward (phase B)", [&] { launch_blend_fwd(b, st, &dm); });
 }
 
 // Binning + blend of a frame whose pairs were just counted (count_pairs) into this image buffer.
 int render_frame(const rr_frame* f, const rr_camera* cam, const int* radii, void* geom_buffer, void* image_buffer,
                  void* binning_buffer, size_t binning_bytes, int num_pairs, float* out_color, float* out_depth,
-                 float* out_normal, void* stream) {
+                 float* out_normal, void* stream, const DistFwdArgs& dm = DistFwdArgs{}) {
     const int P = f->P, W = f->width, H = f->height, L = num_pairs;
     const int cull = (f->flags & RR_FLAG_NO_TILE_CULLING) ? 0 : 1;
     const WsRange reg = std::exchange(g_hand.fwd_ws, WsRange{});  // used by this render, or dropped by it
@@ -564,14 +564,15 @@ int render_frame(const rr_frame* f, const rr_camera* cam, const int* radii, void
     b.normals = out_normal ? gm.normals : nullptr; b.out_normal = out_normal;
     if (L == 0) {  // no pairs: every tile keeps the background (one blend over empty lists)
         b.phase = kBlendSingle;
-        return g_hand.end_render(stage(f, st, RR_STAGE_BLEND_FWD, "blend forward", [&] { launch_blend_fwd(b, st); }));
+        return g_hand.end_render(
+            stage(f, st, RR_STAGE_BLEND_FWD, "blend forward", [&] { launch_blend_fwd(b, st, &dm); }));
     }
     // the split the depth cut makes (its one-phase conditions but "no sampled pair", which leaves
     // phase B empty on the device)
     const Tuning& tu = tuning();
     const bool early = !(f->flags & RR_FLAG_FULL_BINNING) && tu.early_den > 1 && (uint32_t)L >= tu.early_min;
-    return g_hand.end_render(bn.wide ? render_tiles<uint32_t>(f, gm, im, bn, radii, P, W, H, cull, early, b, st)
-                                     : render_tiles<uint16_t>(f, gm, im, bn, radii, P, W, H, cull, early, b, st));
+    return g_hand.end_render(bn.wide ? render_tiles<uint32_t>(f, gm, im, bn, radii, P, W, H, cull, early, b, dm, st)
+                                     : render_tiles<uint16_t>(f, gm, im, bn, radii, P, W, H, cull, early, b, dm, st));
 }
 
 // The tail of rr_forward and rr_forward_from_geometry after the pair count: the binning buffer's
@@ -591,11 +592,14 @@ int finish_forward(const rr_frame* f, const rr_camera* cam, const int* radii, vo
 // Accumulator clear (+ the backward's tile order) and the blend backward: gacc [P][GACC_STRIDE]
 // receives every Gaussian's dmean2D / dconic / dopacity / dcolor sums of the frame.  With dL_ddepth or
 // dL_dalpha (rr_backward_aux) the depth / alpha variant runs and slot 9 receives dL/d(view depth); with
-// dL_dnormal (rr_backward_aux_normal) the normal variant runs and slots 10..12 receive dL/d(normal).
+// dL_dnormal (rr_backward_aux_normal) the normal variant runs and slots 10..12 receive dL/d(normal); with
+// dL_dmoments (rr_backward_aux_dist) the moment variant of either runs (slot 9 also receives the moments'
+// dL/d(view depth)).
 int blend_backward(const rr_frame* f, const rr_camera* cam, const void* geom_buffer, const void* image_buffer,
                    const void* binning_buffer, int L, const float* dL_dpix, float* gacc, hipStream_t st,
                    const float* dL_ddepth = nullptr, const float* dL_dalpha = nullptr,
-                   const float* dL_dnormal = nullptr) {
+                   const float* dL_dnormal = nullptr, const float* dL_dmoments = nullptr, float dist_near = 0.f,
+                   float dist_far = 0.f) {
     const int P = f->P, W = f->width, H = f->height;
     const Geom gm = carve_geom(const_cast<void*>(geom_buffer), P);
     const Img im = carve_img(const_cast<void*>(image_buffer), W, H);
@@ -627,7 +631,10 @@ int blend_backward(const rr_frame* f, const rr_camera* cam, const void* geom_buf
         b.final_T = im.final_T; b.n_contrib = im.n_contrib; b.bg = cam->background; b.dL_dpix = dL_dpix;
         b.gacc = gacc;
         b.order = order;
-        if (dL_dnormal) launch_blend_bwd_normal(b, dL_ddepth, dL_dalpha, dL_dnormal, gm.normals, st);
+        if (dL_dmoments)
+            launch_blend_bwd_dist(b, dL_ddepth, dL_dalpha, dL_dnormal, dL_dnormal ? gm.normals : nullptr, dL_dmoments,
+                                  dist_near, dist_scale_of(dist_near, dist_far), st);
+        else if (dL_dnormal) launch_blend_bwd_normal(b, dL_ddepth, dL_dalpha, dL_dnormal, gm.normals, st);
         else if (dL_ddepth || dL_dalpha) launch_blend_bwd_aux(b, dL_ddepth, dL_dalpha, st);
         else launch_blend_bwd(b, st);
     }
@@ -635,12 +642,13 @@ int blend_backward(const rr_frame* f, const rr_camera* cam, const void* geom_buf
     return RR_OK;
 }
 
-// rr_backward, rr_backward_aux and rr_backward_aux_normal (aux: dL_ddepth, dL_dalpha or dL_dnormal given;
-// dL_dpix may then be null)
+// rr_backward, rr_backward_aux, rr_backward_aux_normal and rr_backward_aux_dist (aux: dL_ddepth, dL_dalpha,
+// dL_dnormal or dL_dmoments given; dL_dpix may then be null)
 int backward_impl(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
                   const void* geom_buffer, const void* image_buffer, const void* binning_buffer, int num_rendered,
                   const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha, const float* dL_dnormal,
-                  void* workspace, size_t workspace_bytes, const rr_grads* out, void* stream);
+                  void* workspace, size_t workspace_bytes, const rr_grads* out, void* stream,
+                  const float* dL_dmoments = nullptr, float dist_near = 0.f, float dist_far = 0.f);
 
 }  // namespace
 
@@ -688,6 +696,22 @@ int rr_forward_render_aux(const rr_frame* f, const rr_camera* cam, const rr_gaus
                         out_depth, out_normal, stream);
 }
 
+int rr_forward_render_dist(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
+                           void* geom_buffer, void* image_buffer, void* binning_buffer, size_t binning_bytes,
+                           int num_pairs, float* out_color, float* out_depth, float* out_normal, float* out_moments,
+                           float dist_near, float dist_far, void* stream) {
+    int rc = validate(f, cam, g, true);
+    if (rc) return rc;
+    if (((f->flags & RR_FLAG_AUX_NORMAL) != 0) != (out_normal != nullptr))
+        return fail(RR_ERR_ARG, "out_normal must be given exactly when RR_FLAG_AUX_NORMAL is set");
+    if (!out_moments) return fail(RR_ERR_ARG, "out_moments is null (rr_forward_render_aux renders without moments)");
+    if (!dist_range_ok(dist_near, dist_far))
+        return fail(RR_ERR_ARG, "dist_near / dist_far must be 0 < near < far, or both 0 (metric depth)");
+    const DistFwdArgs dm{out_moments, dist_near, dist_scale_of(dist_near, dist_far)};
+    return render_frame(f, cam, radii, geom_buffer, image_buffer, binning_buffer, binning_bytes, num_pairs, out_color,
+                        out_depth, out_normal, stream, dm);
+}
+
 int rr_forward_render(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
                       void* geom_buffer, void* image_buffer, void* binning_buffer, size_t binning_bytes,
                       int num_pairs, float* out_color, float* out_depth, void* stream) {
@@ -733,6 +757,16 @@ int rr_backward_aux_normal(const rr_frame* f, const rr_camera* cam, const rr_gau
                          dL_dalpha, dL_dnormal, workspace, workspace_bytes, out, stream);
 }
 
+int rr_backward_aux_dist(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
+                         const void* geom_buffer, const void* image_buffer, const void* binning_buffer,
+                         int num_rendered, const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha,
+                         const float* dL_dnormal, const float* dL_dmoments, float dist_near, float dist_far,
+                         void* workspace, size_t workspace_bytes, const rr_grads* out, void* stream) {
+    return backward_impl(f, cam, g, radii, geom_buffer, image_buffer, binning_buffer, num_rendered, dL_dpix, dL_ddepth,
+                         dL_dalpha, dL_dnormal, workspace, workspace_bytes, out, stream, dL_dmoments, dist_near,
+                         dist_far);
+}
+
 int rr_render_alpha(const rr_frame* f, const void* image_buffer, float* out_alpha, void* stream) {
     if (!f) return fail(RR_ERR_ARG, "null frame");
     const int P = f->P, W = f->width, H = f->height;
@@ -757,12 +791,15 @@ namespace {
 int backward_impl(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
                   const void* geom_buffer, const void* image_buffer, const void* binning_buffer, int num_rendered,
                   const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha, const float* dL_dnormal,
-                  void* workspace, size_t workspace_bytes, const rr_grads* out, void* stream) {
+                  void* workspace, size_t workspace_bytes, const rr_grads* out, void* stream, const float* dL_dmoments,
+                  float dist_near, float dist_far) {
     int rc = validate(f, cam, g, false);
     if (rc) return rc;
+    if (dL_dmoments && !dist_range_ok(dist_near, dist_far))
+        return fail(RR_ERR_ARG, "dist_near / dist_far must be 0 < near < far, or both 0 (metric depth)");
     const int P = f->P, W = f->width, H = f->height, L = num_rendered;
     if (P == 0) return RR_OK;
-    const bool aux = dL_ddepth || dL_dalpha || dL_dnormal;
+    const bool aux = dL_ddepth || dL_dalpha || dL_dnormal || dL_dmoments;
     if (!out || (!dL_dpix && !aux) || !radii || !geom_buffer || !image_buffer || !workspace)
         return fail(RR_ERR_ARG, "null buffer");
     if (dL_dnormal) {
@@ -805,7 +842,7 @@ int backward_impl(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g
     hipStream_t st = (hipStream_t)stream;
     float* gacc = static_cast<float*>(workspace);
     if (int rc2 = blend_backward(f, cam, geom_buffer, image_buffer, binning_buffer, L, dL_dpix, gacc, st, dL_ddepth,
-                                 dL_dalpha, dL_dnormal))
+                                 dL_dalpha, dL_dnormal, dL_dmoments, dist_near, dist_far))
         return rc2;
     {
         StageTimer tm(RR_STAGE_GAUSS_BWD, st);

@@ -54,13 +54,38 @@ namespace rr {
 // profiles/normal_grad_bench.json), so it is built that way.  The other two modes ignore the two
 // extra arguments.  (The body as a shared __device__ function under two kernels, which would
 // keep the other modes' argument block at its old size, compiled them to different code.)
-enum BlendBwdMode { kBlendBwdPlain = 0, kBlendBwdDepth = 1, kBlendBwdNormal = 2 };
+//
+// Moment modes (k_blend_bwd<kBlendBwdDist>, k_blend_bwd<kBlendBwdNormalDist>, rr_backward_aux_dist):
+// the depth-moment maps M1 = sum alpha_i T_i m_i, M2 = sum alpha_i T_i m_i^2 (m_i = m(z_i), the
+// mapped depth of the pair's record: rr_kernels.hpp dist_map) carry gradients too (dm1 = dL/dM1,
+// dm2 = dL/dM2 per pixel).  They are two more channels of the dot product, "colours" m_i and m_i^2
+// with no background term (c . dp + z dd + m dm1 + m^2 dm2, so R and the background numerator stand
+// as written), and dL/dz_i gains alpha_i T_i dm/dz (dm1 + 2 m_i dm2) in slot 9: no new accumulator
+// slot, and the per-Gaussian backward is the depth / normal one.  m_i, m_i^2 and dm/dz are formed
+// once per pair.  They carry dm1[PPL] and dm2[PPL] on top of their base mode: depth + moments is 150
+// VGPRs without scratch at 3 waves per SIMD; depth + normal + moments spills 20 registers there (84 B
+// of scratch per lane) and needs 190 VGPRs, 2 waves per SIMD, without.  Measured interleaved on the
+// bench scene, the spilling build is again the faster one (blend backward 0.314 / 0.300 vs 0.335 /
+// 0.321 ms), so it is built that way (RR_BWD_NDIST_OCC).  The three older
+// modes ignore the three extra arguments and compile to the code they had before.
+enum BlendBwdMode {
+    kBlendBwdPlain = 0,
+    kBlendBwdDepth = 1,
+    kBlendBwdNormal = 2,
+    kBlendBwdDist = 3,        // depth + moments
+    kBlendBwdNormalDist = 4,  // depth + normal + moments
+};
+#ifndef RR_BWD_NDIST_OCC
+#define RR_BWD_NDIST_OCC 3
+#endif
 template <int MODE>
-__global__ __launch_bounds__(64, MODE == kBlendBwdPlain ? 4 : 3) void k_blend_bwd(
-    BlendBwdArgs a, const float* __restrict__ dL_ddepth, const float* __restrict__ dL_dalpha_map,
-    const float* __restrict__ dL_dnormal, const float4* __restrict__ normals) {
+__global__ __launch_bounds__(64, MODE == kBlendBwdPlain ? 4 : MODE == kBlendBwdNormalDist ? RR_BWD_NDIST_OCC : 3)
+void k_blend_bwd(BlendBwdArgs a, const float* __restrict__ dL_ddepth, const float* __restrict__ dL_dalpha_map,
+                 const float* __restrict__ dL_dnormal, const float4* __restrict__ normals,
+                 const float* __restrict__ dL_dmoments, float dist_near, float dist_scale) {
     constexpr bool AUX = MODE != kBlendBwdPlain;
-    constexpr bool NRM = MODE == kBlendBwdNormal;
+    constexpr bool NRM = MODE == kBlendBwdNormal || MODE == kBlendBwdNormalDist;
+    constexpr bool MOM = MODE == kBlendBwdDist || MODE == kBlendBwdNormalDist;
     constexpr int PPL = 4;
     constexpr int B = 64;
     constexpr int NG = NRM ? NGRAD_NRM : AUX ? NGRAD_AUX : NGRAD;
@@ -91,6 +116,7 @@ __global__ __launch_bounds__(64, MODE == kBlendBwdPlain ? 4 : 3) void k_blend_bw
     float T[PPL], tfbg[PPL], dp0[PPL], dp1[PPL], dp2[PPL], R[PPL];
     float dd[AUX ? PPL : 1];  // dL/dD of the lane's pixels (AUX)
     float dn0[NRM ? PPL : 1], dn1[NRM ? PPL : 1], dn2[NRM ? PPL : 1];  // dL/dN of the lane's pixels
+    float dm1[MOM ? PPL : 1], dm2[MOM ? PPL : 1];  // dL/dM1, dL/dM2 of the lane's pixels
     int last[PPL];
 #pragma unroll
     for (int q = 0; q < PPL; q++) {
@@ -114,6 +140,11 @@ __global__ __launch_bounds__(64, MODE == kBlendBwdPlain ? 4 : 3) void k_blend_bw
                 dn0[q] = nrmg ? dL_dnormal[pix] : 0.f;
                 dn1[q] = nrmg ? dL_dnormal[HW + pix] : 0.f;
                 dn2[q] = nrmg ? dL_dnormal[2 * HW + pix] : 0.f;
+            }
+            if constexpr (MOM) {
+                const bool momg = inside && dL_dmoments;
+                dm1[q] = momg ? dL_dmoments[pix] : 0.f;
+                dm2[q] = momg ? dL_dmoments[HW + pix] : 0.f;
             }
         } else {
             dp0[q] = inside ? a.dL_dpix[pix] : 0.f;
@@ -175,6 +206,14 @@ __global__ __launch_bounds__(64, MODE == kBlendBwdPlain ? 4 : 3) void k_blend_bw
             [[maybe_unused]] float g10 = 0.f, g11 = 0.f, g12 = 0.f;  // NRM: dL/dn
             [[maybe_unused]] float4 Nn = make_float4(0.f, 0.f, 0.f, 0.f);
             if constexpr (NRM) Nn = s_n2[cur][j];
+            // MOM: the pair's mapped depth m, m^2, 2 m and dm/dz, once per pair
+            [[maybe_unused]] float mz = 0.f, mz2 = 0.f, mzx2 = 0.f, dmdz = 0.f;
+            if constexpr (MOM) {
+                mz = dist_map(Bv.z, dist_near, dist_scale);
+                mz2 = mz * mz;
+                mzx2 = mz + mz;
+                dmdz = dist_map_dz(Bv.z, dist_near, dist_scale);
+            }
             bool any = false;
             // The conic-side terms are linear in v = e * dL/dalpha with e = opacity G (the unclamped
             // alpha), and a lane's PPL pixels share its column (dx): per pixel only S_v, S_v.dy,
@@ -216,7 +255,13 @@ __global__ __launch_bounds__(64, MODE == kBlendBwdPlain ? 4 : 3) void k_blend_bw
                     T[q] = T[q] * inv;                // T_i, the transmittance in front of this Gaussian
                     const float dchannel_dcolor = alpha * T[q];
                     float cdp = Cc.x * dp0[q] + Cc.y * dp1[q] + Cc.z * dp2[q];
-                    if constexpr (AUX) {
+                    if constexpr (MOM) {  // two more channels, "colours" m_i and m_i^2, and their dL/dz_i
+                        cdp = __builtin_fmaf(Bv.z, dd[q], cdp);
+                        cdp = __builtin_fmaf(mz, dm1[q], cdp);
+                        cdp = __builtin_fmaf(mz2, dm2[q], cdp);
+                        const float dzq = __builtin_fmaf(dmdz, __builtin_fmaf(mzx2, dm2[q], dm1[q]), dd[q]);
+                        g9 = __builtin_fmaf(dchannel_dcolor, dzq, g9);
+                    } else if constexpr (AUX) {
                         cdp = __builtin_fmaf(Bv.z, dd[q], cdp);  // the depth channel: "colour" z_i
                         g9 = __builtin_fmaf(dchannel_dcolor, dd[q], g9);
                     }
@@ -397,18 +442,32 @@ void launch_bwd_prologue(float* gacc, size_t nfloats, int T, const uint32_t* til
 void launch_blend_bwd(const BlendBwdArgs& a, hipStream_t st) {
     const int T = a.gx * a.gy;
     // a.order: from the prologue or the phase-B duplicate
-    if (T > 0) k_blend_bwd<kBlendBwdPlain><<<T, 64, 0, st>>>(a, nullptr, nullptr, nullptr, nullptr);
+    if (T > 0) k_blend_bwd<kBlendBwdPlain><<<T, 64, 0, st>>>(a, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f);
 }
 
 void launch_blend_bwd_aux(const BlendBwdArgs& a, const float* dL_ddepth, const float* dL_dalpha, hipStream_t st) {
     const int T = a.gx * a.gy;
-    if (T > 0) k_blend_bwd<kBlendBwdDepth><<<T, 64, 0, st>>>(a, dL_ddepth, dL_dalpha, nullptr, nullptr);
+    if (T > 0) k_blend_bwd<kBlendBwdDepth><<<T, 64, 0, st>>>(a, dL_ddepth, dL_dalpha, nullptr, nullptr, nullptr, 0.f, 0.f);
 }
 
 void launch_blend_bwd_normal(const BlendBwdArgs& a, const float* dL_ddepth, const float* dL_dalpha,
                              const float* dL_dnormal, const float4* normals, hipStream_t st) {
     const int T = a.gx * a.gy;
-    if (T > 0) k_blend_bwd<kBlendBwdNormal><<<T, 64, 0, st>>>(a, dL_ddepth, dL_dalpha, dL_dnormal, normals);
+    if (T > 0)
+        k_blend_bwd<kBlendBwdNormal><<<T, 64, 0, st>>>(a, dL_ddepth, dL_dalpha, dL_dnormal, normals, nullptr, 0.f, 0.f);
+}
+
+void launch_blend_bwd_dist(const BlendBwdArgs& a, const float* dL_ddepth, const float* dL_dalpha,
+                           const float* dL_dnormal, const float4* normals, const float* dL_dmoments, float near,
+                           float scale, hipStream_t st) {
+    const int T = a.gx * a.gy;
+    if (T == 0) return;
+    if (dL_dnormal)
+        k_blend_bwd<kBlendBwdNormalDist><<<T, 64, 0, st>>>(a, dL_ddepth, dL_dalpha, dL_dnormal, normals, dL_dmoments,
+                                                          near, scale);
+    else
+        k_blend_bwd<kBlendBwdDist><<<T, 64, 0, st>>>(a, dL_ddepth, dL_dalpha, nullptr, nullptr, dL_dmoments, near,
+                                                    scale);
 }
 
 // Accumulated alpha A = 1 - T_final of the frame last rendered into the image buffer (rr_render_alpha).

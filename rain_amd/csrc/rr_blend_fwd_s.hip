@@ -34,12 +34,23 @@ typedef __attribute__((address_space(4))) const u2v cu2v_s;
 
 // NW waves per 16x16 tile, PIX = 4/NW pixels per lane: lane l of wave w owns column l%16 and rows
 // l/16 + 4*(w*PIX + k), k < PIX.  G pairs per group (their alphas formed before the blend).
-template <int NW, bool AUX>
+// MOM: the depth-moment maps M1 = sum w m, M2 = sum w m^2 (w = alpha T, m the mapped depth of the
+// pair's record, dist_map) are blended too, per-pixel state like Dp (rr_forward_render_dist).  DIST
+// is DistFwdArgs for those instantiations and empty for the others, which are the kernels they were:
+// the same name and argument block, the same instructions but for a move scheduled elsewhere or a
+// register pair renamed.  A trailing DistFwdArgs argument for all of them moved
+// the others' hidden-argument offsets; a shared __device__ body under two kernels compiled them to
+// different code.
+__device__ __forceinline__ DistFwdArgs dist_of() { return DistFwdArgs{}; }
+__device__ __forceinline__ const DistFwdArgs& dist_of(const DistFwdArgs& d) { return d; }
+template <int NW, bool AUX, typename... DIST>
 #ifndef RR_FWD_S_OCC
 #define RR_FWD_S_OCC 1
 #endif
-__global__ __launch_bounds__(64 * NW, RR_FWD_S_OCC) void k_blend_fwd_s(BlendFwdArgs a) {
+__global__ __launch_bounds__(64 * NW, RR_FWD_S_OCC) void k_blend_fwd_s(BlendFwdArgs a, DIST... dist) {
 #pragma clang fp contract(off)  // blend_e2's rounding: every fma below is explicit
+    constexpr bool MOM = sizeof...(DIST) != 0;
+    const DistFwdArgs dm = dist_of(dist...);
     constexpr int PIX = 4 / NW;
 #ifndef RR_FWD_S_GROUP
 #define RR_FWD_S_GROUP 3
@@ -65,7 +76,7 @@ __global__ __launch_bounds__(64 * NW, RR_FWD_S_OCC) void k_blend_fwd_s(BlendFwdA
     const size_t HW = (size_t)a.H * a.W;
 
     int py[PIX];
-    float pfy[PIX], T[PIX], C0[PIX], C1[PIX], C2[PIX], Dp[PIX], N0[PIX], N1[PIX], N2[PIX];
+    float pfy[PIX], T[PIX], C0[PIX], C1[PIX], C2[PIX], Dp[PIX], N0[PIX], N1[PIX], N2[PIX], M1[PIX], M2[PIX];
     uint32_t last[PIX];
     bool inside[PIX];
 #pragma unroll
@@ -74,7 +85,7 @@ __global__ __launch_bounds__(64 * NW, RR_FWD_S_OCC) void k_blend_fwd_s(BlendFwdA
         pfy[k] = (float)py[k];
         inside[k] = px < a.W && py[k] < a.H;
         T[k] = inside[k] ? 1.f : -1.f;  // T < 0: closed (pixels outside the image start closed)
-        C0[k] = C1[k] = C2[k] = Dp[k] = N0[k] = N1[k] = N2[k] = 0.f;
+        C0[k] = C1[k] = C2[k] = Dp[k] = N0[k] = N1[k] = N2[k] = M1[k] = M2[k] = 0.f;
         last[k] = 0;
     }
     const u2v r0 = ((cu2v_s*)a.ranges)[tile];
@@ -100,6 +111,10 @@ __global__ __launch_bounds__(64 * NW, RR_FWD_S_OCC) void k_blend_fwd_s(BlendFwdA
                     N0[k] = a.out_normal[pix];
                     N1[k] = a.out_normal[HW + pix];
                     N2[k] = a.out_normal[2 * HW + pix];
+                }
+                if (MOM) {
+                    M1[k] = dm.out_moments[pix];
+                    M2[k] = dm.out_moments[HW + pix];
                 }
                 last[k] = nc & ~kDoneBit;
             }
@@ -128,6 +143,12 @@ __global__ __launch_bounds__(64 * NW, RR_FWD_S_OCC) void k_blend_fwd_s(BlendFwdA
         P2X px2[G];
 #pragma unroll
         for (int u = 0; u < G; u++) px2[u] = blend_p2_x(ra[u].z, ra[u].w, rb[u].y, ra[u].x - pfx);
+        float mz[G], mz2[G];  // MOM: the pairs' mapped depths, once per pair
+#pragma unroll
+        for (int u = 0; u < G; u++) {
+            mz[u] = MOM ? dist_map(rb[u].z, dm.near, dm.scale) : 0.f;
+            mz2[u] = mz[u] * mz[u];
+        }
 #pragma unroll
         for (int k = 0; k < PIX; k++) {
 #pragma unroll
@@ -163,6 +184,10 @@ __global__ __launch_bounds__(64 * NW, RR_FWD_S_OCC) void k_blend_fwd_s(BlendFwdA
                     N0[k] = __builtin_fmaf(rn[u].x, wgt, N0[k]);
                     N1[k] = __builtin_fmaf(rn[u].y, wgt, N1[k]);
                     N2[k] = __builtin_fmaf(rn[u].z, wgt, N2[k]);
+                }
+                if (MOM) {
+                    M1[k] = __builtin_fmaf(mz[u], wgt, M1[k]);
+                    M2[k] = __builtin_fmaf(mz2[u], wgt, M2[k]);
                 }
                 T[k] = sat ? -fabsf(T[k]) : testT;
                 last[k] = blend ? k1 : last[k];
@@ -272,6 +297,10 @@ __global__ __launch_bounds__(64 * NW, RR_FWD_S_OCC) void k_blend_fwd_s(BlendFwdA
                         a.out_normal[HW + pix] = N1[k];
                         a.out_normal[2 * HW + pix] = N2[k];
                     }
+                    if (MOM) {
+                        dm.out_moments[pix] = M1[k];
+                        dm.out_moments[HW + pix] = M2[k];
+                    }
                 }
             }
             return;
@@ -295,6 +324,10 @@ __global__ __launch_bounds__(64 * NW, RR_FWD_S_OCC) void k_blend_fwd_s(BlendFwdA
                 a.out_normal[pix] = N0[k];
                 a.out_normal[HW + pix] = N1[k];
                 a.out_normal[2 * HW + pix] = N2[k];
+            }
+            if (MOM) {
+                dm.out_moments[pix] = M1[k];
+                dm.out_moments[HW + pix] = M2[k];
             }
         }
     }
@@ -322,7 +355,7 @@ void set_fwd_trace(void* dev_buf) { g_fwd_trace = static_cast<uint32_t*>(dev_buf
 
 // Phase A (or a single-phase frame): 2 waves per tile (2 pixels per lane); phase B, whose few open
 // tiles each set the launch's length: 4 (1 pixel per lane).
-void launch_blend_fwd(const BlendFwdArgs& a_in, hipStream_t st) {
+void launch_blend_fwd(const BlendFwdArgs& a_in, hipStream_t st, const DistFwdArgs* dist) {
     BlendFwdArgs a = a_in;
     a.trace = g_fwd_trace;
     const int T = a.gx * a.gy;
@@ -333,7 +366,15 @@ void launch_blend_fwd(const BlendFwdArgs& a_in, hipStream_t st) {
     const size_t per_block = (size_t)64 * waves * 16;
     const int nc = (a.clear && a.clear_n4) ? (int)std::min<size_t>((a.clear_n4 + per_block - 1) / per_block, 4096) : 0;
     const int nb = T + nc;
-    if (waves == 4) {
+    if (dist && dist->out_moments) {  // the depth-moment maps (rr_forward_render_dist)
+        if (waves == 4) {
+            if (aux) k_blend_fwd_s<4, true, DistFwdArgs><<<nb, 256, 0, st>>>(a, *dist);
+            else k_blend_fwd_s<4, false, DistFwdArgs><<<nb, 256, 0, st>>>(a, *dist);
+        } else {
+            if (aux) k_blend_fwd_s<2, true, DistFwdArgs><<<nb, 128, 0, st>>>(a, *dist);
+            else k_blend_fwd_s<2, false, DistFwdArgs><<<nb, 128, 0, st>>>(a, *dist);
+        }
+    } else if (waves == 4) {
         if (aux) k_blend_fwd_s<4, true><<<nb, 256, 0, st>>>(a);
         else k_blend_fwd_s<4, false><<<nb, 256, 0, st>>>(a);
     } else {

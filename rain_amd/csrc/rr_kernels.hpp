@@ -117,6 +117,29 @@ struct BlendFwdArgs {
     size_t clear_n4;
 };
 
+// The depth-moment maps of the distortion loss (rr_forward_render_dist / rr_backward_aux_dist):
+// M1 = sum w_i m_i, M2 = sum w_i m_i^2 with w_i = alpha_i T_i and m_i = m(z_i) the mapped depth of
+// the pair's splat record.  near == 0 (and far == 0): m(z) = z.  Else the NDC depth
+// m(z) = scale (1 - near / z), scale = far / (far - near), dm/dz = scale near / z^2.
+struct DistFwdArgs {
+    float* out_moments;  // [2,H,W]: M1, M2 (null: no moment maps)
+    float near, scale;
+};
+// (every lane forms them for every pair: v_rcp_f32, 1 ulp, instead of a division's dozen instructions.
+// Measured on the bench scene, per frame: moment forward blend 0.175 -> 0.152 ms, backward 0.270 -> 0.250)
+__device__ __forceinline__ float dist_map(float z, float near, float scale) {
+    return near == 0.f ? z : scale * (1.f - near * __builtin_amdgcn_rcpf(z));
+}
+__device__ __forceinline__ float dist_map_dz(float z, float near, float scale) {
+    const float iz = __builtin_amdgcn_rcpf(z);
+    return near == 0.f ? 1.f : scale * near * (iz * iz);
+}
+// host: the scale of a validated (near, far) pair
+inline float dist_scale_of(float near, float far) { return near == 0.f ? 1.f : far / (far - near); }
+inline bool dist_range_ok(float near, float far) {
+    return (near == 0.f && far == 0.f) || (near > 0.f && far > near && far <= 3.0e38f);
+}
+
 struct BlendBwdArgs {
     int W, H, gx, gy;
     const uint2* ranges;
@@ -293,7 +316,8 @@ bool launch_duplicate(const DupArgs<K>& d, hipStream_t st);
 // the slots reserved added to *d.n_total (rr_forward.hip k_dup_gather)
 template <typename K>
 void launch_dup_gather(const DupArgs<K>& d, hipStream_t st);
-void launch_blend_fwd(const BlendFwdArgs& a, hipStream_t st);
+// dist (optional): also blend the depth-moment maps
+void launch_blend_fwd(const BlendFwdArgs& a, hipStream_t st, const DistFwdArgs* dist = nullptr);
 void launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t st);
 
 void launch_blend_bwd(const BlendBwdArgs& a, hipStream_t st);  // a.order: from launch_bwd_prologue
@@ -307,6 +331,12 @@ void launch_blend_bwd_aux(const BlendBwdArgs& a, const float* dL_ddepth, const f
 // dL/d(normal) into accumulator slots 10..12.
 void launch_blend_bwd_normal(const BlendBwdArgs& a, const float* dL_ddepth, const float* dL_dalpha,
                              const float* dL_dnormal, const float4* normals, hipStream_t st);
+// The moment variants (rr_backward_aux_dist): dL_dmoments is the [2,H,W] planar gradient of the
+// depth-moment maps (dL/dM1, dL/dM2).  Without dL_dnormal the depth + moments mode runs (normals
+// unused), with it the depth + normal + moments mode.  dL/dm_i times dm/dz is added into slot 9.
+void launch_blend_bwd_dist(const BlendBwdArgs& a, const float* dL_ddepth, const float* dL_dalpha,
+                           const float* dL_dnormal, const float4* normals, const float* dL_dmoments, float near,
+                           float scale, hipStream_t st);
 void launch_render_alpha(const float* final_T, size_t n, float* out, hipStream_t st);  // out = 1 - final_T
 // clears the nfloats gradient accumulators and, with order, writes the backward's tile order
 // order_flag (may be null): *order_flag == T means the order was already computed this frame

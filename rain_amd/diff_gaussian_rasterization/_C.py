@@ -9,7 +9,9 @@ implemented over the C ABI in include/rain_raster.h.
 Beyond the reference (opt-in): ``rasterize_gaussians_backward_depth`` also takes gradients of the
 depth map and of the accumulated alpha, and ``accumulated_alpha`` returns that alpha map
 (include/rain_raster.h rr_backward_aux, rr_render_alpha); ``rasterize_gaussians_backward_normal``
-takes a gradient of the aux normal map of ``rasterize_gaussians_aux`` as well (rr_backward_aux_normal).
+takes a gradient of the aux normal map of ``rasterize_gaussians_aux`` as well (rr_backward_aux_normal);
+``rasterize_gaussians_dist`` also renders the depth-moment maps of the distortion loss and
+``rasterize_gaussians_backward_dist`` takes their gradient (rr_forward_render_dist, rr_backward_aux_dist).
 
 Differences that are deliberate and invisible to callers: scratch buffers are sized by the C
 ABI's *_bytes() queries instead of grown through std::function callbacks; outputs the kernels
@@ -89,9 +91,25 @@ def rasterize_gaussians_aux(background, means3D, colors, opacity, scales, rotati
                       prefiltered, debug, low_pass, True)
 
 
+def rasterize_gaussians_dist(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+                             viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
+                             prefiltered, debug, low_pass, dist_near, dist_far, normal=False):
+    """rasterize_gaussians plus the depth-moment maps moments [2,H,W] = (sum w m, sum w m^2), w = alpha T,
+    m the mapped depth (include/rain_raster.h rr_forward_render_dist: NDC depth for 0 < dist_near <
+    dist_far, metric depth for 0, 0), and with `normal` the aux normal map: returns (num_rendered, color,
+    radii, depth, normal [3,H,W] or None, moments, geomBuffer, binningBuffer, imgBuffer).  The buffers are
+    valid for rasterize_gaussians_backward_dist."""
+    out = _rasterize(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+                     viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
+                     prefiltered, debug, low_pass, bool(normal), (float(dist_near), float(dist_far)))
+    return out[:5] + (out[8],) + out[5:8]
+
+
 def _rasterize(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
-               prefiltered, debug, low_pass, normal):
+               prefiltered, debug, low_pass, normal, dist=None):
+    """(num_rendered, color, radii, depth, normal, geom, binning, img) and, with dist = (near, far), the
+    moment maps as a ninth entry."""
     if means3D.ndimension() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
     P = means3D.size(0)
@@ -102,7 +120,8 @@ def _rasterize(background, means3D, colors, opacity, scales, rotations, scale_mo
     if P == 0:
         return (0, torch.zeros((NUM_CHANNELS, H, W), **fopts), torch.zeros((0,), dtype=torch.int32, device=device),
                 torch.zeros((1, H, W), **fopts), torch.zeros((3, H, W), **fopts) if normal else None,
-                torch.empty((0,), **u8), torch.empty((0,), **u8), torch.empty((0,), **u8))
+                torch.empty((0,), **u8), torch.empty((0,), **u8), torch.empty((0,), **u8)) + \
+            ((torch.zeros((2, H, W), **fopts),) if dist is not None else ())
     L = N.raster()
     M = sh.size(1) if sh.size(0) != 0 else 0
     keep = dict(
@@ -133,6 +152,14 @@ def _rasterize(background, means3D, colors, opacity, scales, rotations, scale_mo
             "rasterize_gaussians")
     num_rendered, num_pairs = nr.value, npairs.value
     binning = torch.empty((L.rr_binning_bytes(num_pairs, W, H) if num_pairs > 0 else 0,), **u8)
+    if dist is not None:
+        moments = torch.empty((2, H, W), **fopts)
+        N.check(L.rr_forward_render_dist(ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs), _ptr(radii),
+                                         _ptr(geom), _ptr(img), _ptr(binning), binning.numel(), num_pairs,
+                                         _ptr(out_color), _ptr(out_depth), _ptr(out_normal), _ptr(moments),
+                                         dist[0], dist[1], stream),
+                "rasterize_gaussians_dist")
+        return num_rendered, out_color, radii, out_depth, out_normal, geom, binning, img, moments
     N.check(L.rr_forward_render_aux(ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs), _ptr(radii),
                                     _ptr(geom), _ptr(img), _ptr(binning), binning.numel(), num_pairs,
                                     _ptr(out_color), _ptr(out_depth), _ptr(out_normal), stream),
@@ -178,21 +205,42 @@ def rasterize_gaussians_backward_normal(background, means3D, radii, colors, scal
                      binningBuffer, imageBuffer, debug, low_pass, dL_dout_depth, dL_dout_alpha, dL_dout_normal)
 
 
+def rasterize_gaussians_backward_dist(background, means3D, radii, colors, scales, rotations, scale_modifier,
+                                      cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh,
+                                      degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, low_pass,
+                                      dL_dout_depth, dL_dout_alpha, dL_dout_normal, dL_dout_moments, dist_near,
+                                      dist_far):
+    """rasterize_gaussians_backward_normal plus a gradient of the depth-moment maps (dL_dout_moments
+    [2,H,W] = dL/dM1, dL/dM2; rr_backward_aux_dist) of a frame rendered by rasterize_gaussians_dist with
+    the same dist_near / dist_far (and, for a normal gradient, normal=True).  Any of the five output
+    gradients may be an empty tensor ("absent": zero), but not all of them; with dL_dout_moments absent
+    this is rasterize_gaussians_backward_normal.  The moments reach dL_dmeans3D through the view depth
+    and every geometric gradient through alpha_i.  Same 8-tuple."""
+    return _backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
+                     viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R,
+                     binningBuffer, imageBuffer, debug, low_pass, dL_dout_depth, dL_dout_alpha, dL_dout_normal,
+                     dL_dout_moments, (float(dist_near), float(dist_far)))
+
+
 def _present(t):
     return t is not None and t.numel() != 0
 
 
 def _backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
               projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
-              imageBuffer, debug, low_pass, dL_dout_depth, dL_dout_alpha, dL_dout_normal=None):
+              imageBuffer, debug, low_pass, dL_dout_depth, dL_dout_alpha, dL_dout_normal=None, dL_dout_moments=None,
+              dist=(0.0, 0.0)):
     P = means3D.size(0)
     nrm = _present(dL_dout_normal)
-    aux = _present(dL_dout_depth) or _present(dL_dout_alpha) or nrm
+    mom = _present(dL_dout_moments)
+    aux = _present(dL_dout_depth) or _present(dL_dout_alpha) or nrm or mom
     if aux:  # the frame's size from whichever output gradient is there
-        ref = next(t for t in (dL_dout_color, dL_dout_depth, dL_dout_alpha, dL_dout_normal) if _present(t))
+        ref = next(t for t in (dL_dout_color, dL_dout_depth, dL_dout_alpha, dL_dout_normal, dL_dout_moments)
+                   if _present(t))
         H, W = ref.size(-2), ref.size(-1)
         for name, t, c in (("dL_dout_color", dL_dout_color, NUM_CHANNELS), ("dL_dout_depth", dL_dout_depth, 1),
-                           ("dL_dout_alpha", dL_dout_alpha, 1), ("dL_dout_normal", dL_dout_normal, 3)):
+                           ("dL_dout_alpha", dL_dout_alpha, 1), ("dL_dout_normal", dL_dout_normal, 3),
+                           ("dL_dout_moments", dL_dout_moments, 2)):
             if _present(t) and t.numel() != c * H * W:
                 raise RuntimeError(f"{name} must have {c} x {H} x {W} elements (got {tuple(t.shape)})")
     else:
@@ -213,7 +261,8 @@ def _backward(background, means3D, radii, colors, scales, rotations, scale_modif
         dpix=_dev_f32(dL_dout_color, device, "dL_dout_color"), radii=radii.contiguous(),
         ddepth=_dev_f32(dL_dout_depth, device, "dL_dout_depth") if aux else None,
         dalpha=_dev_f32(dL_dout_alpha, device, "dL_dout_alpha") if aux else None,
-        dnormal=_dev_f32(dL_dout_normal, device, "dL_dout_normal") if nrm else None)
+        dnormal=_dev_f32(dL_dout_normal, device, "dL_dout_normal") if nrm else None,
+        dmoments=_dev_f32(dL_dout_moments, device, "dL_dout_moments") if mom else None)
     # opacities are not needed by the backward (the reference does not pass them either)
     frame = _frame(P, degree, M, W, H, tan_fovx, tan_fovy, scale_modifier, low_pass, False, debug)
     if nrm:  # the forward was rasterize_gaussians_aux
@@ -229,7 +278,14 @@ def _backward(background, means3D, radii, colors, scales, rotations, scale_modif
                                                "dL_dcov3D", "dL_dsh", "dL_dscales", "dL_drotations")])
     ws = torch.empty((L.rr_backward_workspace_bytes(P),), dtype=torch.uint8, device=device)
     stream = N.stream_of(means3D)
-    if nrm:
+    if mom:
+        N.check(L.rr_backward_aux_dist(ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs), _ptr(keep["radii"]),
+                                       _ptr(geomBuffer), _ptr(imageBuffer), _ptr(binningBuffer), int(R),
+                                       _ptr(keep["dpix"]), _ptr(keep["ddepth"]), _ptr(keep["dalpha"]),
+                                       _ptr(keep["dnormal"]), _ptr(keep["dmoments"]), dist[0], dist[1], _ptr(ws),
+                                       ws.numel(), ctypes.byref(grads), stream),
+                "rasterize_gaussians_backward_dist")
+    elif nrm:
         N.check(L.rr_backward_aux_normal(ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs),
                                          _ptr(keep["radii"]), _ptr(geomBuffer), _ptr(imageBuffer),
                                          _ptr(binningBuffer), int(R), _ptr(keep["dpix"]), _ptr(keep["ddepth"]),

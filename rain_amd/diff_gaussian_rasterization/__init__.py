@@ -19,6 +19,7 @@ from . import _C
 
 _MSG_COLOR = 'Please provide excatly one of either SHs or precomputed colors!'  # reference text, typo included
 _MSG_COV = 'Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!'
+_MSG_DIST = 'forward_distortion needs 0 < dist_near < dist_far, or both 0 (metric depth)'
 _MSG_NORMAL = 'render_depth_normal needs the scale/rotation pair (normals come from the scale axes)'
 
 
@@ -175,6 +176,47 @@ class _RasterizeGaussiansNormal(torch.autograd.Function):
         return d_means3D, d_means2D, d_sh, d_colors, d_opacities, d_scales, d_rotations, d_cov3D, None
 
 
+class _RasterizeGaussiansDist(torch.autograd.Function):
+    """_RasterizeGaussiansNormal plus the differentiable depth-moment maps of the distortion loss (no
+    reference counterpart; GaussianRasterizer.forward_distortion): returns (color, radii, depth, alpha,
+    normal or None, moments) with moments [2,H,W] = (sum alpha_i T_i m_i, sum alpha_i T_i m_i^2)."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                raster_settings, dist_near, dist_far, normal):
+        s = raster_settings
+        args = _forward_args(s, means3D, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, sh) + \
+            (float(dist_near), float(dist_far), bool(normal))
+        num_rendered, color, radii, depth, nmap, moments, geom, binning, img = _invoke(
+            _C.rasterize_gaussians_dist, args, s.debug, "snapshot_fw.dump",
+            "\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
+        alpha = _C.accumulated_alpha(img, s.image_height, s.image_width)
+        ctx.raster_settings = s
+        ctx.num_rendered = num_rendered
+        ctx.dist = (float(dist_near), float(dist_far))
+        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning,
+                              img)
+        ctx.mark_non_differentiable(radii)
+        ctx.set_materialize_grads(False)
+        return color, radii, depth, alpha, nmap, moments
+
+    @staticmethod
+    def backward(ctx, grad_out_color, grad_radii, grad_depth, grad_alpha, grad_normal, grad_moments):
+        gs = (grad_out_color, grad_depth, grad_alpha, grad_normal, grad_moments)
+        if all(g is None for g in gs):
+            return (None,) * 12
+        s = ctx.raster_settings
+        empty = torch.Tensor([])  # "absent" (a NULL pointer in the library)
+        grad_out_color, grad_depth, grad_alpha, grad_normal, grad_moments = (empty if g is None else g for g in gs)
+        args = _backward_args(s, ctx.saved_tensors, ctx.num_rendered, grad_out_color) + (
+            grad_depth, grad_alpha, grad_normal, grad_moments) + ctx.dist
+        d_means2D, d_colors, d_opacities, d_means3D, d_cov3D, d_sh, d_scales, d_rotations = _invoke(
+            _C.rasterize_gaussians_backward_dist, args, s.debug, "snapshot_bw.dump",
+            "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
+        return (d_means3D, d_means2D, d_sh, d_colors, d_opacities, d_scales, d_rotations, d_cov3D, None, None, None,
+                None)
+
+
 def _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp):
     """The reference's two argument checks (__init__.py:177-187)."""
     if (shs is None) == (colors_precomp is None):
@@ -243,6 +285,26 @@ class GaussianRasterizer(nn.Module):
         return _RasterizeGaussiansNormal.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                                cov3D_precomp, self.raster_settings)
 
+    def forward_distortion(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None,
+                           rotations=None, cov3D_precomp=None, dist_near=0.2, dist_far=100.0, normal=False):
+        """forward_depth() plus the differentiable depth-moment maps of the depth-distortion loss
+        (opt-in): returns (color [3,H,W], radii [P], depth [1,H,W], alpha [1,H,W], normal [3,H,W] or None,
+        moments [2,H,W]).  moments = (M1, M2) = (sum w_i m_i, sum w_i m_i^2) with w_i = alpha_i T_i and m_i
+        the mapped view depth: the NDC depth far/(far-near) (1 - near/z) for 0 < dist_near < dist_far, z
+        itself for dist_near = dist_far = 0.  The per-pixel distortion sum_{i>j} w_i w_j (m_i - m_j)^2 is
+        alpha * M2 - M1^2 (rain_amd.loss.fused_distortion_loss).  With `normal` the aux normal map of
+        forward_normal() is rendered and differentiated too (needs the scale/rotation pair)."""
+        _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp)
+        if normal and cov3D_precomp is not None:
+            raise Exception(_MSG_NORMAL)
+        near, far = float(dist_near), float(dist_far)
+        if not ((near == 0.0 and far == 0.0) or (0.0 < near < far < float("inf"))):
+            raise Exception(_MSG_DIST)
+        shs, colors_precomp, scales, rotations, cov3D_precomp = _absent_as_empty(shs, colors_precomp, scales,
+                                                                                 rotations, cov3D_precomp)
+        return _RasterizeGaussiansDist.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+                                             cov3D_precomp, self.raster_settings, near, far, bool(normal))
+
     @torch.no_grad()
     def render_depth_normal(self, means3D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None):
         """Forward only, with the auxiliary outputs of BASELINE configs[4]: returns (color [3,H,W],
@@ -260,4 +322,4 @@ class GaussianRasterizer(nn.Module):
 
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "_RasterizeGaussians",
-           "_RasterizeGaussiansDepth", "_RasterizeGaussiansNormal", "_C"]
+           "_RasterizeGaussiansDepth", "_RasterizeGaussiansNormal", "_RasterizeGaussiansDist", "_C"]

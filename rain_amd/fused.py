@@ -45,6 +45,9 @@ class RawFrame:
     ws: torch.Tensor | None = None
     # the aux normal map [3,H,W] of a frame rendered with normal=True (RR_FLAG_AUX_NORMAL), else None
     normal: torch.Tensor | None = None
+    # the depth-moment maps [2,H,W] of a frame rendered with dist=(near, far), else None, and that pair
+    moments: torch.Tensor | None = None
+    dist: tuple | None = None
 
 
 class BinningCache:
@@ -64,27 +67,30 @@ class BinningCache:
 
 
 def forward(model, camera, bg: torch.Tensor, low_pass: float, scale_modifier: float = 1.0,
-            cache: BinningCache | None = None, normal: bool = False):
+            cache: BinningCache | None = None, normal: bool = False, dist: tuple | None = None):
     """Render `camera` from `model` (a GaussianModel) in raw-parameter mode.
     Returns (color [3,H,W], radii [P] int32, depth [1,H,W], RawFrame).  With `cache` the binning
     buffer is reused (see BinningCache) and must not be needed by an earlier frame's pending
     backward.  With `normal` the frame also renders the aux normal map (RR_FLAG_AUX_NORMAL), left in
     the RawFrame's `normal` field ([3,H,W]); backward(dL_dnormal=...) differentiates it.  Such a
-    frame always runs its own preprocess (it cannot be the `next_frame` of an earlier backward)."""
+    frame always runs its own preprocess (it cannot be the `next_frame` of an earlier backward).
+    With `dist` = (dist_near, dist_far) the frame also renders the depth-moment maps of the distortion
+    loss (rr_forward_render_dist), left in the RawFrame's `moments` field ([2,H,W]);
+    backward(dL_dmoments=...) differentiates them.  It runs its own preprocess as well."""
     params = (model._xyz, model._features_dc, model._features_rest, model._opacity, model._scaling,
               model._rotation)
     return forward_params(params, model.active_sh_degree, int(camera.image_width), int(camera.image_height),
                           math.tan(camera.FoVx * 0.5), math.tan(camera.FoVy * 0.5), camera.world_view_transform,
                           camera.full_proj_transform, camera.camera_center, bg, low_pass, scale_modifier, cache,
-                          normal)
+                          normal, dist)
 
 
 def forward_params(params, sh_degree: int, W: int, H: int, tanfovx: float, tanfovy: float, viewmatrix, projmatrix,
                    campos, bg: torch.Tensor, low_pass: float, scale_modifier: float = 1.0,
-                   cache: BinningCache | None = None, normal: bool = False):
+                   cache: BinningCache | None = None, normal: bool = False, dist: tuple | None = None):
     """forward() on explicit raw parameters (xyz, f_dc, f_rest, opacity, scaling, rotation) — the
     GaussianModel attributes before activation — and camera values as render() puts them in
-    GaussianRasterizationSettings.  `normal`: see forward()."""
+    GaussianRasterizationSettings.  `normal`, `dist`: see forward()."""
     xyz = params[0]
     dev = xyz.device
     if dev.type != "cuda":
@@ -119,7 +125,10 @@ def forward_params(params, sh_degree: int, W: int, H: int, tanfovx: float, tanfo
     ws = _register_workspace(L, P, dev)
     # the aux normal frame goes through the two-stage calls (rr_forward renders no normal map)
     nmap = torch.empty((3, H, W), **fo) if normal else None
-    if P > 0 and cache is not None and not normal:
+    if dist is not None:
+        dist = (float(dist[0]), float(dist[1]))
+    mom = torch.empty((2, H, W), **fo) if dist is not None else None
+    if P > 0 and cache is not None and not normal and dist is None:
         binning = cache.buf if cache.buf is not None and cache.buf.device == dev else torch.empty((0,), **u8)
         need = ctypes.c_size_t(0)
         rc = L.rr_forward(ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs), _p(radii), _p(geom), geom.numel(),
@@ -139,7 +148,13 @@ def forward_params(params, sh_degree: int, W: int, H: int, tanfovx: float, tanfo
                                                ctypes.byref(npairs), stream), "fused forward")
     nbin = L.rr_binning_bytes(npairs.value, W, H) if npairs.value > 0 else 0
     binning = cache.get(nbin, dev) if cache is not None and nbin > 0 else torch.empty((nbin,), **u8)
-    if P > 0:
+    if P > 0 and dist is not None:
+        _check_render(L, L.rr_forward_render_dist(ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs),
+                                                  _p(radii), _p(geom), _p(img), _p(binning), binning.numel(),
+                                                  npairs.value, _p(color), _p(depth), _p(nmap), _p(mom), dist[0],
+                                                  dist[1], stream),
+                      "fused forward")
+    elif P > 0:
         _check_render(L, L.rr_forward_render_aux(ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs),
                                                  _p(radii), _p(geom), _p(img), _p(binning), binning.numel(),
                                                  npairs.value, _p(color), _p(depth), _p(nmap), stream),
@@ -149,7 +164,9 @@ def forward_params(params, sh_degree: int, W: int, H: int, tanfovx: float, tanfo
         depth.zero_()
         if normal:
             nmap.zero_()
-    st = RawFrame(frame, cam, gs, (keep, params), radii, geom, img, binning, nr.value, P, M, ws, nmap)
+        if mom is not None:
+            mom.zero_()
+    st = RawFrame(frame, cam, gs, (keep, params), radii, geom, img, binning, nr.value, P, M, ws, nmap, mom, dist)
     return color, radii, depth, st
 
 
@@ -251,7 +268,7 @@ def forward_next(nxt: NextFrame, model, cache: BinningCache | None = None):
 def backward(st: RawFrame, dL_dpix: torch.Tensor, grads: dict | None, stats: tuple | None = None,
              adam: "N.RRAdam | None" = None, dmeans2D: torch.Tensor | None = None, next_frame: NextFrame | None = None,
              dL_ddepth: torch.Tensor | None = None, dL_dalpha: torch.Tensor | None = None,
-             dL_dnormal: torch.Tensor | None = None):
+             dL_dnormal: torch.Tensor | None = None, dL_dmoments: torch.Tensor | None = None):
     """Write dLoss/d(raw parameter) into grads['xyz'|'f_dc'|'f_rest'|'opacity'|'scaling'|'rotation']
     (contiguous fp32 tensors of the parameter shapes, fully overwritten) and, if `stats` =
     (grad_accum [P,1], denom [P,1], max_radii2D [P]) is given, update the densification statistics
@@ -267,18 +284,23 @@ def backward(st: RawFrame, dL_dpix: torch.Tensor, grads: dict | None, stats: tup
     be None.
     `dL_dnormal` ([3,H,W] fp32, optional): gradient of the aux normal map of a frame rendered with
     forward(normal=True), added likewise (rr_backward_aux_normal): it reaches the rotation directly
-    and everything else through alpha_i."""
+    and everything else through alpha_i.
+    `dL_dmoments` ([2,H,W] fp32, optional): gradient of the depth-moment maps of a frame rendered with
+    forward(dist=(near, far)), added likewise (rr_backward_aux_dist, with the frame's near / far): it
+    reaches xyz through the view depth and everything else through alpha_i."""
     if st.P == 0:
         return
     L = N.raster()
-    aux = dL_ddepth is not None or dL_dalpha is not None or dL_dnormal is not None
+    aux = dL_ddepth is not None or dL_dalpha is not None or dL_dnormal is not None or dL_dmoments is not None
+    if dL_dmoments is not None and st.dist is None:
+        raise RuntimeError("rain_amd.fused.backward: dL_dmoments needs a frame rendered with forward(dist=(near, far))")
     if dL_dpix is None and not aux:
         raise RuntimeError("rain_amd.fused.backward: no output gradient given")
     npix = st.frame.width * st.frame.height
-    maps = [None, None, None]
+    maps = [None, None, None, None]
     if aux:
         for i, (name, t, c) in enumerate((("dL_ddepth", dL_ddepth, 1), ("dL_dalpha", dL_dalpha, 1),
-                                          ("dL_dnormal", dL_dnormal, 3))):
+                                          ("dL_dnormal", dL_dnormal, 3), ("dL_dmoments", dL_dmoments, 2))):
             if t is not None:
                 if t.dtype != torch.float32 or t.numel() != c * npix:
                     raise RuntimeError(f"rain_amd.fused: {name} must be a float32 [{c}, H, W] tensor")
@@ -307,6 +329,13 @@ def backward(st: RawFrame, dL_dpix: torch.Tensor, grads: dict | None, stats: tup
         frame.flags |= N.RR_FLAG_WORKSPACE_REGISTERED
     else:
         ws = torch.empty((L.rr_backward_workspace_bytes(st.P),), dtype=torch.uint8, device=dev)
+    if maps[3] is not None:
+        N.check(L.rr_backward_aux_dist(ctypes.byref(frame), ctypes.byref(st.cam), ctypes.byref(st.gs), _p(st.radii),
+                                       _p(st.geom), _p(st.img), _p(st.binning), st.num_rendered,
+                                       _p(dpix) if dL_dpix is not None else None, _p(maps[0]), _p(maps[1]),
+                                       _p(maps[2]), _p(maps[3]), st.dist[0], st.dist[1], _p(ws), ws.numel(),
+                                       ctypes.byref(out), N.stream_of(dpix)), "fused backward (distortion)")
+        return
     if maps[2] is not None:
         N.check(L.rr_backward_aux_normal(ctypes.byref(frame), ctypes.byref(st.cam), ctypes.byref(st.gs),
                                          _p(st.radii), _p(st.geom), _p(st.img), _p(st.binning), st.num_rendered,
@@ -461,3 +490,46 @@ class RasterizeRawParamsNormal(torch.autograd.Function):
                  dL_dnormal=grad_normal)
         return (grads["xyz"], grads["f_dc"], grads["f_rest"], grads["opacity"], grads["scaling"], grads["rotation"], d2,
                 None, None, None, None, None, None, None, None, None, None, None)
+
+
+class RasterizeRawParamsDist(torch.autograd.Function):
+    """RasterizeRawParamsDepth plus the differentiable depth-moment maps of the distortion loss
+    (render(dist_grad=True)), and with `normal` the aux normal map too: returns (color, radii, depth,
+    alpha, normal or None, moments) — moments = (sum alpha_i T_i m_i, sum alpha_i T_i m_i^2) [2,H,W] —
+    and its backward adds their gradients to the others' (rr_backward_aux_dist)."""
+
+    @staticmethod
+    def forward(ctx, xyz, f_dc, f_rest, opacity, scaling, rotation, means2D, sh_degree, W, H, tanfovx, tanfovy,
+                viewmatrix, projmatrix, campos, bg, low_pass, scale_modifier, dist_near, dist_far, normal):
+        color, radii, depth, st = forward_params((xyz, f_dc, f_rest, opacity, scaling, rotation), sh_degree, W, H,
+                                                 tanfovx, tanfovy, viewmatrix, projmatrix, campos, bg, low_pass,
+                                                 scale_modifier, normal=bool(normal), dist=(dist_near, dist_far))
+        alpha = accumulated_alpha(st)
+        keep, _p6 = st.keep
+        ctx.save_for_backward(xyz, f_dc, f_rest, opacity, scaling, rotation, st.radii, st.geom, st.img, st.binning,
+                              st.ws, *keep)
+        ctx.desc = (st.frame, st.cam, st.gs, st.num_rendered, st.P, st.M, st.dist)
+        ctx.mark_non_differentiable(radii)
+        ctx.set_materialize_grads(False)
+        return color, radii, depth, alpha, st.normal, st.moments
+
+    @staticmethod
+    def backward(ctx, grad_color, _grad_radii, grad_depth, grad_alpha, grad_normal, grad_moments):
+        if all(g is None for g in (grad_color, grad_depth, grad_alpha, grad_normal, grad_moments)):
+            return (None,) * 21
+        xyz, f_dc, f_rest, opacity, scaling, rotation, radii, geom, img, binning, ws, *keep = ctx.saved_tensors
+        frame, cam, gs, num_rendered, P, M, dist = ctx.desc
+        p = (xyz, f_dc, opacity, scaling, rotation, f_rest)  # kernel order
+        ws_first = ws if not getattr(ctx, "ws_used", False) else None
+        ctx.ws_used = True
+        st = RawFrame(frame, cam, gs, (tuple(keep), p), radii, geom, img, binning, num_rendered, P, M, ws_first,
+                      dist=dist)
+        grads = dict(xyz=torch.empty_like(p[0]), f_dc=torch.empty_like(p[1]), opacity=torch.empty_like(p[2]),
+                     scaling=torch.empty_like(p[3]), rotation=torch.empty_like(p[4]), f_rest=torch.empty_like(p[5]))
+        d2 = torch.empty((st.P, 3), dtype=torch.float32, device=p[0].device)
+        if st.P == 0:
+            d2.zero_()
+        backward(st, grad_color, grads, dmeans2D=d2, dL_ddepth=grad_depth, dL_dalpha=grad_alpha,
+                 dL_dnormal=grad_normal, dL_dmoments=grad_moments)
+        return (grads["xyz"], grads["f_dc"], grads["f_rest"], grads["opacity"], grads["scaling"], grads["rotation"], d2,
+                None, None, None, None, None, None, None, None, None, None, None, None, None, None)

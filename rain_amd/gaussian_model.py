@@ -103,6 +103,13 @@ class OptimizationParams:
         # (rain_amd.loss.fused_geometry_loss) added to the loss from `lambda_normal_from_iter` on
         self.lambda_normal = 0.0
         self.lambda_normal_from_iter = 7000
+        # opt-in (no reference counterpart): weight of the depth-distortion term
+        # (rain_amd.loss.fused_distortion_loss) added from `lambda_dist_from_iter` on, over the NDC depth
+        # between dist_near and dist_far (0, 0: the metric depth)
+        self.lambda_dist = 0.0
+        self.lambda_dist_from_iter = 3000
+        self.dist_near = 0.2
+        self.dist_far = 100.0
         for k, v in kw.items():
             setattr(self, k, v)
 

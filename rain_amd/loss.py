@@ -281,6 +281,117 @@ def fused_geometry_loss(depth, alpha, normal, tanfovx, tanfovy, lambda_normal=0.
                                     alpha_min)
 
 
+def _dist_args(alpha, moments, lambda_dist):
+    """Checked, contiguous (alpha, moments) and the shared head of the rl_dist_* argument lists."""
+    if alpha.device.type != "cuda":
+        raise RuntimeError("distortion loss: tensors must be on a HIP device (no CPU fallback)")
+    H, W = alpha.shape[-2:]
+    for name, t, c in (("alpha", alpha, 1), ("moments", moments, 2)):
+        if t.dtype != torch.float32 or t.numel() != c * H * W or t.device != alpha.device:
+            raise RuntimeError(f"distortion loss: {name} must be a float32 [{c}, {H}, {W}] tensor on the alpha's device")
+    alpha, moments = alpha.contiguous(), moments.contiguous()
+    return alpha, moments, [alpha.data_ptr(), moments.data_ptr(), H, W, float(lambda_dist)], H, W
+
+
+def _dist_grad_buffers(alpha, moments, d_alpha):
+    if d_alpha is not None and (not d_alpha.is_contiguous() or d_alpha.dtype != torch.float32 or
+                                d_alpha.numel() != alpha.numel() or d_alpha.device != alpha.device):
+        raise RuntimeError("distortion loss: d_alpha must be a contiguous float32 tensor of alpha's size and device")
+    dA = d_alpha if d_alpha is not None else torch.empty_like(alpha)
+    return dA, torch.empty_like(moments)
+
+
+def distortion_loss_forward(alpha, moments, lambda_dist):
+    """Depth-distortion loss lambda_dist * mean(A M2 - M1^2), forward (include/rain_loss.h
+    rl_dist_forward).  Returns (loss scalar, parts [2] = {loss, unweighted mean})."""
+    from . import _native as N
+
+    L = N.loss_lib()
+    alpha, moments, head, H, W = _dist_args(alpha, moments, lambda_dist)
+    dev = alpha.device
+    ws = torch.empty((L.rl_dist_workspace_bytes(H, W),), dtype=torch.uint8, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    parts = torch.empty((2,), dtype=torch.float32, device=dev)
+    rc = L.rl_dist_forward(*head, ws.data_ptr(), ws.numel(), loss.data_ptr(), parts.data_ptr(), N.stream_of(alpha))
+    if rc:
+        raise RuntimeError(L.rl_last_error().decode())
+    return loss, parts
+
+
+def distortion_loss_backward(alpha, moments, lambda_dist, grad_loss=None, d_alpha=None):
+    """(dL/dalpha, dL/dmoments) scaled by grad_loss (a device scalar; None = 1).  With `d_alpha` (a
+    contiguous float32 tensor of alpha's size) the alpha gradient is ADDED into it and it is returned;
+    otherwise a fresh tensor is written."""
+    from . import _native as N
+
+    L = N.loss_lib()
+    alpha, moments, head, H, W = _dist_args(alpha, moments, lambda_dist)
+    dA, dM = _dist_grad_buffers(alpha, moments, d_alpha)
+    if grad_loss is None:
+        grad_loss = _ones(alpha.device)
+    g = grad_loss.reshape(1).contiguous().float()
+    rc = L.rl_dist_backward(*head, g.data_ptr(), dA.data_ptr(), dM.data_ptr(), int(d_alpha is not None),
+                            N.stream_of(alpha))
+    if rc:
+        raise RuntimeError(L.rl_last_error().decode())
+    return dA, dM
+
+
+def distortion_loss_forward_backward(alpha, moments, lambda_dist, d_alpha=None, grad_loss=None):
+    """Forward and backward at once (the training step's form): (loss, parts, dA, dM), bitwise
+    distortion_loss_forward's loss / parts and distortion_loss_backward's gradients, in two launches.
+    `d_alpha`: an existing alpha gradient (e.g. geometry_loss_forward_backward's) to add into."""
+    from . import _native as N
+
+    L = N.loss_lib()
+    alpha, moments, head, H, W = _dist_args(alpha, moments, lambda_dist)
+    dev = alpha.device
+    ws = torch.empty((L.rl_dist_workspace_bytes(H, W),), dtype=torch.uint8, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    parts = torch.empty((2,), dtype=torch.float32, device=dev)
+    dA, dM = _dist_grad_buffers(alpha, moments, d_alpha)
+    if grad_loss is None:
+        grad_loss = _ones(dev)
+    g = grad_loss.reshape(1).contiguous().float()
+    rc = L.rl_dist_forward_backward(*head, ws.data_ptr(), ws.numel(), loss.data_ptr(), parts.data_ptr(), g.data_ptr(),
+                                    dA.data_ptr(), dM.data_ptr(), int(d_alpha is not None), N.stream_of(alpha))
+    if rc:
+        raise RuntimeError(L.rl_last_error().decode())
+    return loss, parts, dA, dM
+
+
+class _FusedDistortionLoss(torch.autograd.Function):
+    """lambda_dist * mean(A M2 - M1^2) in HIP kernels (rain_amd/csrc/geom_loss.hip, rl_dist_*)."""
+
+    @staticmethod
+    def forward(ctx, alpha, moments, lambda_dist):
+        alpha, moments = alpha.contiguous(), moments.contiguous()
+        ctx.lam = float(lambda_dist)
+        loss, parts = distortion_loss_forward(alpha, moments, ctx.lam)
+        ctx.save_for_backward(alpha, moments)
+        ctx.mark_non_differentiable(parts)
+        ctx.set_materialize_grads(False)
+        return loss, parts
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_parts):
+        if grad_loss is None:
+            return None, None, None
+        alpha, moments = ctx.saved_tensors
+        dA, dM = distortion_loss_backward(alpha, moments, ctx.lam, grad_loss)
+        return dA, dM, None
+
+
+def fused_distortion_loss(alpha, moments, lambda_dist):
+    """Depth-distortion loss (Mip-NeRF 360 / 2DGS) on the maps render(dist_grad=True) returns: alpha
+    [1,H,W] = Σ α T and depth_moments [2,H,W] = (Σ α T m, Σ α T m²): lambda_dist · mean(A·M2 − M1²), which
+    is the mean over pixels of Σ_{i>j} w_i w_j (m_i − m_j)².  Returns (loss, parts) with parts =
+    [loss, unweighted mean] (device, no sync, not differentiable); gradients reach alpha and moments."""
+    if alpha.dim() != 3 or alpha.device.type != "cuda":
+        raise RuntimeError("fused_distortion_loss expects [1,H,W] / [2,H,W] tensors on a HIP device")
+    return _FusedDistortionLoss.apply(alpha, moments, lambda_dist)
+
+
 @lru_cache(maxsize=8)
 def _sep_windows(window_size, channels, device, dtype):
     g = window_1d(window_size, 1.5).to(device=device, dtype=dtype)

@@ -69,10 +69,13 @@ class PipelineParams:
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
-           low_pass=0.3, depth_grad=False, normal_grad=False):
+           low_pass=0.3, depth_grad=False, normal_grad=False, dist_grad=False, dist_near=0.2, dist_far=100.0):
     """The reference's render(); `depth_grad` adds a differentiable "depth" and "alpha" to the
     dictionary, `normal_grad` (which implies depth_grad) a differentiable aux "normal" map [3,H,W]
-    as well (sum alpha_i T_i n_i, GaussianRasterizer.forward_normal)."""
+    as well (sum alpha_i T_i n_i, GaussianRasterizer.forward_normal).  `dist_grad` (which implies
+    depth_grad and composes with normal_grad) adds the differentiable "depth_moments" [2,H,W] =
+    (sum w m, sum w m^2) of the mapped depth m (NDC depth between dist_near and dist_far, or the metric
+    depth for 0, 0; GaussianRasterizer.forward_distortion) and "distortion" [1,H,W] = alpha M2 - M1^2."""
     if normal_grad and pipe.compute_cov3D_python:
         raise Exception("render(normal_grad=True) needs the scale/rotation pair (not compute_cov3D_python): "
                         "normals come from the scale axes")
@@ -105,6 +108,12 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
                     screenspace_points, pc.active_sh_degree, raster_settings.image_width,
                     raster_settings.image_height, tanfovx, tanfovy, raster_settings.viewmatrix,
                     raster_settings.projmatrix, raster_settings.campos, bg_color, low_pass, scaling_modifier)
+        if dist_grad:
+            from .fused import RasterizeRawParamsDist
+
+            rendered_image, radii, depth, alpha, normal, moments = RasterizeRawParamsDist.apply(
+                *raw_args, float(dist_near), float(dist_far), bool(normal_grad))
+            return _dist_package(rendered_image, screenspace_points, radii, depth, alpha, normal, moments)
         if normal_grad:
             rendered_image, radii, depth, alpha, normal = RasterizeRawParamsNormal.apply(*raw_args)
             return {"render": rendered_image, "viewspace_points": screenspace_points,
@@ -141,6 +150,12 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     else:
         colors_precomp = override_color
 
+    if dist_grad:
+        rendered_image, radii, depth, alpha, normal, moments = rasterizer.forward_distortion(
+            means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors_precomp, opacities=opacity,
+            scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp, dist_near=dist_near, dist_far=dist_far,
+            normal=normal_grad)
+        return _dist_package(rendered_image, screenspace_points, radii, depth, alpha, normal, moments)
     if normal_grad:
         rendered_image, radii, depth, alpha, normal = rasterizer.forward_normal(
             means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors_precomp, opacities=opacity,
@@ -158,6 +173,16 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
                                               rotations=rotations, cov3D_precomp=cov3D_precomp)
     return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
             "radii": radii, "depth": depth}
+
+
+def _dist_package(rendered_image, screenspace_points, radii, depth, alpha, normal, moments):
+    """render(dist_grad=True)'s dictionary ("normal" only with normal_grad)."""
+    pkg = {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
+           "radii": radii, "depth": depth, "alpha": alpha, "depth_moments": moments,
+           "distortion": alpha * moments[1:2] - moments[0:1] * moments[0:1]}
+    if normal is not None:
+        pkg["normal"] = normal
+    return pkg
 
 
 @torch.no_grad()

@@ -29,7 +29,7 @@ import torch
 import torch.distributed as dist
 
 from .gaussian_model import GaussianModel, OptimizationParams, low_pass_schedule
-from .loss import fused_geometry_loss, fused_l1_ssim_loss
+from .loss import fused_distortion_loss, fused_geometry_loss, fused_l1_ssim_loss
 from .optim import sharded_adam_step
 from .renderer import PipelineParams, render
 
@@ -235,6 +235,7 @@ class Trainer:
         if self.fused and not (dev.type == "cuda" and loss_fn is None and plain_pipe):
             raise ValueError("fused step needs a HIP device, the default loss and the default pipeline")
         self._geometry_weight(0)  # a non-zero lambda_normal on the sharded paths is refused here already
+        self._distortion_weight(0)  # and so is a non-zero lambda_dist
 
     def _low_pass_and_view(self, iteration):
         g, opt, cfg = self.g, self.opt, self.cfg
@@ -315,6 +316,21 @@ class Trainer:
                              "GPU or set lambda_normal = 0")
         return lam if iteration >= int(getattr(self.opt, "lambda_normal_from_iter", 0)) else 0.0
 
+    def _distortion_weight(self, iteration: int) -> float:
+        """The weight of the depth-distortion term at `iteration`: OptimizationParams.lambda_dist from
+        lambda_dist_from_iter on, else 0 (today's step, untouched)."""
+        lam = float(getattr(self.opt, "lambda_dist", 0.0) or 0.0)
+        if lam <= 0.0:
+            return 0.0
+        if self.sharded:
+            raise ValueError("lambda_dist > 0 needs the single-GPU step: the Gaussian-sharded / multi-rank steps "
+                             "have no depth-moment backward (k_gauss_bwd_views has no depth variant); train on one "
+                             "GPU or set lambda_dist = 0")
+        return lam if iteration >= int(getattr(self.opt, "lambda_dist_from_iter", 0)) else 0.0
+
+    def _dist_range(self):
+        return float(getattr(self.opt, "dist_near", 0.2)), float(getattr(self.opt, "dist_far", 100.0))
+
     def step(self, iteration: int, sync_loss: bool = False) -> StepInfo:
         if self.fused:
             return self._step_fused(iteration, sync_loss)
@@ -377,9 +393,10 @@ class Trainer:
 
     def _step_fused(self, iteration: int, sync_loss: bool) -> StepInfo:
         from . import fused
-        from .loss import geometry_loss_forward_backward, l1_ssim_forward_backward
+        from .loss import distortion_loss_forward_backward, geometry_loss_forward_backward, l1_ssim_forward_backward
 
         lam_n = self._geometry_weight(iteration)  # refuses the sharded steps when the weight is set
+        lam_t = self._distortion_weight(iteration)  # likewise
         if self._owner is not None:
             return self._step_owner(iteration, sync_loss)
 
@@ -392,8 +409,8 @@ class Trainer:
             if nxt is not None and (nxt.P != g.get_xyz.shape[0] or nxt.frame.D != g.active_sh_degree
                                     or sig != self._params_signature()):
                 nxt = None  # the parameters changed since step s-1's backward preprocessed this frame
-            if lam_n:
-                nxt = None  # a frame with the aux normal map runs its own preprocess
+            if lam_n or lam_t:
+                nxt = None  # a frame with the aux normal map or the moment maps runs its own preprocess
         else:
             vidx, cam = self._low_pass_and_view(iteration)
             nxt = None
@@ -424,7 +441,8 @@ class Trainer:
         # inside that backward (no densify / reset replacing parameters) and the SH degree stays
         next_frame = None
         if (fuse_adam and self.fuse_next and not self.sharded and iteration + 1 < opt.iterations
-                and not self._sh_steps_up(iteration + 1) and not lam_n and not self._geometry_weight(iteration + 1)):
+                and not self._sh_steps_up(iteration + 1) and not lam_n and not self._geometry_weight(iteration + 1)
+                and not lam_t and not self._distortion_weight(iteration + 1)):
             low_pass_now = self.low_pass
             vidx1, cam1 = self._low_pass_and_view(iteration + 1)
             next_frame = fused.prepare_next(g, cam1, self.background, self.low_pass)
@@ -436,17 +454,28 @@ class Trainer:
                 image, radii, _depth, st = fused.forward_next(nxt, g, cache=cache)
             else:
                 image, radii, _depth, st = fused.forward(g, cam, self.background, self.low_pass, cache=cache,
-                                                         normal=bool(lam_n))
+                                                         normal=bool(lam_n),
+                                                         dist=self._dist_range() if lam_t else None)
             # loss and dL/dimage in one call (bitwise the separate forward / backward)
             loss, _parts, dimg = l1_ssim_forward_backward(image, gt, opt.lambda_dssim)
-            if lam_n:
-                # depth-normal consistency on the frame's depth / alpha / normal maps: two more launches,
-                # its three map gradients join the colour's in the one backward
-                gloss, _gparts, dD, dA, dN = geometry_loss_forward_backward(
-                    _depth, fused.accumulated_alpha(st), st.normal, st.frame.tan_fovx, st.frame.tan_fovy, lam_n)
-                fused.backward(st, dimg, grads, stats, adam=adam, dL_ddepth=dD, dL_dalpha=dA, dL_dnormal=dN)
-                if sync_loss:
-                    loss = loss + gloss
+            if lam_n or lam_t:
+                alpha = fused.accumulated_alpha(st)
+                dD = dA = dN = dM = None
+                if lam_n:
+                    # depth-normal consistency on the frame's depth / alpha / normal maps: two more launches,
+                    # its three map gradients join the colour's in the one backward
+                    gloss, _gparts, dD, dA, dN = geometry_loss_forward_backward(
+                        _depth, alpha, st.normal, st.frame.tan_fovx, st.frame.tan_fovy, lam_n)
+                    if sync_loss:
+                        loss = loss + gloss
+                if lam_t:
+                    # depth distortion on the alpha / moment maps: two more launches; its alpha gradient is
+                    # added into the consistency term's, both map-gradient sets go into the one backward
+                    tloss, _tparts, dA, dM = distortion_loss_forward_backward(alpha, st.moments, lam_t, d_alpha=dA)
+                    if sync_loss:
+                        loss = loss + tloss
+                fused.backward(st, dimg, grads, stats, adam=adam, dL_ddepth=dD, dL_dalpha=dA, dL_dnormal=dN,
+                               dL_dmoments=dM)
             else:
                 fused.backward(st, dimg, grads, stats, adam=adam, next_frame=next_frame)
             densified = self._finish(iteration, flat, densify_now, reset_now, adam_done=fuse_adam)
@@ -516,6 +545,7 @@ class Trainer:
         """The reference-API step: render() through GaussianRasterizer + autograd (train.py:109-147)."""
         g, opt = self.g, self.opt
         lam_n = self._geometry_weight(iteration)
+        lam_t = self._distortion_weight(iteration)
         vidx, cam = self._low_pass_and_view(iteration)
         densify_phase = iteration < opt.densify_until_iter
         densify_now, reset_now = self._events(iteration)
@@ -527,7 +557,12 @@ class Trainer:
             for p in g.params():
                 p.grad = None
 
-        pkg = render(cam, g, self.pipe, self.background, low_pass=self.low_pass, normal_grad=bool(lam_n))
+        if lam_t:
+            near, far = self._dist_range()
+            pkg = render(cam, g, self.pipe, self.background, low_pass=self.low_pass, normal_grad=bool(lam_n),
+                         dist_grad=True, dist_near=near, dist_far=far)
+        else:
+            pkg = render(cam, g, self.pipe, self.background, low_pass=self.low_pass, normal_grad=bool(lam_n))
         image, vsp, vis, radii = pkg["render"], pkg["viewspace_points"], pkg["visibility_filter"], pkg["radii"]
         gt = self.gt[vidx]
         # (1-λ)·L1 + λ·(1-SSIM) (train.py:113-114), by default one fused HIP forward/backward
@@ -536,6 +571,8 @@ class Trainer:
             loss = loss + fused_geometry_loss(pkg["depth"], pkg["alpha"], pkg["normal"],
                                               math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5),
                                               lambda_normal=lam_n)[0]
+        if lam_t:  # + lambda_dist · depth distortion (rain_amd/csrc/geom_loss.hip, rl_dist_*)
+            loss = loss + fused_distortion_loss(pkg["alpha"], pkg["depth_moments"], lam_t)[0]
         loss.backward()
 
         with torch.no_grad():
