@@ -263,6 +263,52 @@ int rr_backward_aux(const rr_frame* f, const rr_camera* cam, const rr_gaussians*
                     void* workspace, size_t workspace_bytes, const rr_grads* out, void* stream);
 
 /*
+ * Camera-pose gradients (opt-in): rr_backward_aux plus the gradients of the three camera arrays of
+ * rr_camera, for pose refinement, tracking and joint pose-and-scene optimisation.  viewmatrix [16],
+ * projmatrix [16] (the full projection) and campos [3] are three INDEPENDENT inputs, exactly as
+ * rr_camera passes them, and each gradient has its input's memory layout (dL_dviewmatrix viewed as
+ * [4,4] is the gradient of the torch tensor world_view_transform as given).  What feeds each, with
+ * the colour path's conventions:
+ *   view    through t = (mean, 1) . view of the EWA Jacobian J, through the 3x3 block W of T = J W,
+ *           and through the view depth t.z of the depth map (accumulator slot 9).  A clamped EWA
+ *           coordinate is a constant, no mask for the 0.99 alpha clamp.  Entries 3, 7, 11, 15 (read
+ *           by no kernel) get exactly 0.
+ *   proj    through mean2D only: p_hom = (mean, 1) . proj, mean2D = p_hom.xy / (p_hom.w + 1e-7).  The
+ *           z row (entries 2, 6, 10, 14) gets exactly 0.
+ *   campos  through the SH view direction (mean - campos) / |.|, with the colour clamp mask of the SH
+ *           backward; exactly 0 with colors_precomp.
+ * Culling, radii, tile lists and the depth order are discrete and contribute nothing; a Gaussian with
+ * radii <= 0 contributes exactly 0.
+ *
+ * cg == NULL: exactly rr_backward_aux (the same dispatch and kernels).  Otherwise the three outputs
+ * and the scratch (rr_camera_grad_scratch_bytes(P), 16-B aligned, no pre-zeroing) are required; the
+ * outputs are fully written (zeros for P == 0 or a frame with nothing visible), bitwise reproducible
+ * given the same accumulators (per-workgroup sums, then one fixed-order pass in double; no float
+ * atomics).  dL_dpix alone, or any of the three output gradients, may be given as in rr_backward_aux;
+ * raw-parameter mode (RR_FLAG_RAW_PARAMS) is allowed; every gradient of rr_grads and the densification
+ * statistics are rr_backward_aux's, and RR_FLAG_WORKSPACE_REGISTERED behaves as there.
+ * Refused with RR_ERR_ARG before any device work: a null output or scratch, rr_grads.adam and
+ * rr_grads.next (the fused step and the next frame's preprocess get no camera variant).  Too small a
+ * scratch is RR_ERR_CAPACITY.  Not covered yet (follow-ups): a camera gradient together with
+ * dL_dnormal (one more outer product with the view block) or dL_dmoments (they already ride slot 9) —
+ * rr_backward_aux_normal / rr_backward_aux_dist take no rr_camera_grads — and the sharded
+ * rr_gauss_backward_views.
+ */
+typedef struct rr_camera_grads {
+    float* dL_dviewmatrix;  /* [16] */
+    float* dL_dprojmatrix;  /* [16] */
+    float* dL_dcampos;      /* [3]  */
+    void*  scratch;         /* rr_camera_grad_scratch_bytes(P), 16-B aligned */
+    size_t scratch_bytes;
+} rr_camera_grads;
+size_t rr_camera_grad_scratch_bytes(int P);
+int rr_backward_camera(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
+                       const void* geom_buffer, const void* image_buffer, const void* binning_buffer,
+                       int num_rendered, const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha,
+                       void* workspace, size_t workspace_bytes, const rr_grads* out, const rr_camera_grads* cg,
+                       void* stream);
+
+/*
  * rr_backward_aux plus a gradient of the aux normal map (RR_FLAG_AUX_NORMAL, rr_forward_render_aux):
  * N(p) = sum_i alpha_i T_i n_i, with n_i the view-space unit normal of Gaussian i (the world axis of
  * its smallest scale, R[:, k], rotated by the view matrix, flipped to face the camera, normalised;

@@ -73,6 +73,12 @@ class RRGrads(ctypes.Structure):
                [("adam", ctypes.POINTER(RRAdam)), ("next", ctypes.POINTER(RRNextFrame))]
 
 
+class RRCameraGrads(ctypes.Structure):
+    """include/rain_raster.h rr_camera_grads: the camera-gradient outputs of rr_backward_camera."""
+    _fields_ = [("dL_dviewmatrix", ctypes.c_void_p), ("dL_dprojmatrix", ctypes.c_void_p),
+                ("dL_dcampos", ctypes.c_void_p), ("scratch", ctypes.c_void_p), ("scratch_bytes", ctypes.c_size_t)]
+
+
 class RRView(ctypes.Structure):
     _fields_ = [("viewmatrix", ctypes.c_void_p), ("projmatrix", ctypes.c_void_p), ("campos", ctypes.c_void_p),
                 ("tan_fovx", ctypes.c_float), ("tan_fovy", ctypes.c_float), ("low_pass", ctypes.c_float),
@@ -102,7 +108,8 @@ RASTER_SYMBOLS = ["rr_geometry_bytes", "rr_image_bytes", "rr_binning_bytes", "rr
                   "rr_forward_render_geometry",
                   "rr_backward_records", "rr_gauss_backward_views", "rr_set_forward_workspace",
                   "rr_backward_aux", "rr_render_alpha", "rr_backward_aux_normal",
-                  "rr_forward_render_dist", "rr_backward_aux_dist"]
+                  "rr_forward_render_dist", "rr_backward_aux_dist",
+                  "rr_camera_grad_scratch_bytes", "rr_backward_camera"]
 
 _raster = None
 _knn = None
@@ -144,6 +151,12 @@ def raster():
         # rr_backward plus dL_ddepth, dL_dalpha after dL_dpix (depth / accumulated-alpha gradients)
         L.rr_backward_aux.restype = ci
         L.rr_backward_aux.argtypes = [fp, cp, gp, vp, vp, vp, vp, ci, vp, vp, vp, vp, sz, ctypes.POINTER(RRGrads), vp]
+        # rr_backward_aux plus the camera-gradient block before the stream
+        L.rr_camera_grad_scratch_bytes.restype = sz
+        L.rr_camera_grad_scratch_bytes.argtypes = [ci]
+        L.rr_backward_camera.restype = ci
+        L.rr_backward_camera.argtypes = [fp, cp, gp, vp, vp, vp, vp, ci, vp, vp, vp, vp, sz, ctypes.POINTER(RRGrads),
+                                         ctypes.POINTER(RRCameraGrads), vp]
         L.rr_backward_aux_normal.restype = ci
         L.rr_backward_aux_normal.argtypes = [fp, cp, gp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, sz,
                                              ctypes.POINTER(RRGrads), vp]

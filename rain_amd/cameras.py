@@ -90,6 +90,82 @@ class Camera:
                       self.znear, self.zfar, str(device))
 
 
+def skew(w: torch.Tensor) -> torch.Tensor:
+    """[3] -> the 3x3 cross-product matrix [w]x."""
+    z = torch.zeros((), dtype=w.dtype, device=w.device)
+    return torch.stack([torch.stack([z, -w[2], w[1]]), torch.stack([w[2], z, -w[0]]), torch.stack([-w[1], w[0], z])])
+
+
+class _KeepBase(torch.autograd.Function):
+    """The value of `base`, the gradient of `computed` (CameraPose at zero deltas: E = I reproduces the
+    base matrix's values, but a product with I turns a -0 entry into +0; selecting the base keeps the
+    matrix bitwise, and the gradient still reaches the deltas)."""
+
+    @staticmethod
+    def forward(ctx, computed, base):
+        return base.clone()
+
+    @staticmethod
+    def backward(ctx, grad):
+        return grad, None
+
+
+class CameraPose(torch.nn.Module):
+    """A Camera with a learnable pose correction (pose refinement, tracking; render(pose_grad=True)).
+
+    With the base world-to-view rotation R and translation t of `camera`, the parameters
+    rot_delta [3] (an axis-angle vector, left-multiplied) and trans_delta [3], both zero-initialised, and
+    E = matrix_exp(skew(rot_delta)) (whose gradient is finite at 0): R' = E R, t' = E t + trans_delta.
+    It exposes, differentiably, what render() reads of a Camera: world_view_transform ([R' t'; 0 1]^T,
+    contiguous), full_proj_transform (world_view_transform @ projection_matrix), camera_center
+    (-R'^T t', closed form), and FoVx / FoVy / image_width / image_height.  At zero deltas the two
+    matrices equal the base camera's.  `dtype`: the parameters' and matrices' type (float64 for
+    reference computations; the rasterizer takes float32)."""
+
+    def __init__(self, camera: Camera, dtype=torch.float32):
+        super().__init__()
+        self.FoVx, self.FoVy = camera.FoVx, camera.FoVy
+        self.image_width, self.image_height = camera.image_width, camera.image_height
+        self.uid = camera.uid
+        w2c = camera.world_view_transform.detach().to(dtype).transpose(0, 1)
+        self.register_buffer("base_wvt", camera.world_view_transform.detach().to(dtype).contiguous())
+        self.register_buffer("base_fpt", camera.full_proj_transform.detach().to(dtype).contiguous())
+        self.register_buffer("base_R", w2c[:3, :3].contiguous())
+        self.register_buffer("base_t", w2c[:3, 3].contiguous())
+        self.register_buffer("projection_matrix", camera.projection_matrix.detach().to(dtype).contiguous())
+        dev = camera.world_view_transform.device
+        self.rot_delta = torch.nn.Parameter(torch.zeros(3, dtype=dtype, device=dev))
+        self.trans_delta = torch.nn.Parameter(torch.zeros(3, dtype=dtype, device=dev))
+
+    def rotation_translation(self):
+        """(R' [3,3], t' [3]) of the corrected world-to-view transform."""
+        E = torch.linalg.matrix_exp(skew(self.rot_delta))
+        return E @ self.base_R, E @ self.base_t + self.trans_delta
+
+    @property
+    def world_view_transform(self):
+        R, t = self.rotation_translation()
+        bottom = torch.zeros((3, 1), dtype=R.dtype, device=R.device)
+        one = torch.ones((1, 1), dtype=R.dtype, device=R.device)
+        # rows of the transpose: [R'^T 0], [t'^T 1]
+        wvt = torch.cat([torch.cat([R.transpose(0, 1), bottom], 1), torch.cat([t.view(1, 3), one], 1)], 0).contiguous()
+        if not bool(torch.cat([self.rot_delta.detach(), self.trans_delta.detach()]).any()):
+            wvt = _KeepBase.apply(wvt, self.base_wvt)  # zero deltas: the base camera's matrix, bitwise
+        return wvt
+
+    @property
+    def full_proj_transform(self):
+        fpt = self.world_view_transform.unsqueeze(0).bmm(self.projection_matrix.unsqueeze(0)).squeeze(0)
+        if not bool(torch.cat([self.rot_delta.detach(), self.trans_delta.detach()]).any()):
+            fpt = _KeepBase.apply(fpt, self.base_fpt)  # (the base's product may come from another device)
+        return fpt
+
+    @property
+    def camera_center(self):
+        R, t = self.rotation_translation()
+        return -(R.transpose(0, 1) @ t)
+
+
 def look_at_R_T(eye: np.ndarray, target=np.zeros(3), up=np.array([0.0, 0.0, 1.0])):
     """COLMAP-style (R, T) for a camera at ``eye`` looking at ``target``: x right, y down, z forward.
 

@@ -648,7 +648,8 @@ int backward_impl(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g
                   const void* geom_buffer, const void* image_buffer, const void* binning_buffer, int num_rendered,
                   const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha, const float* dL_dnormal,
                   void* workspace, size_t workspace_bytes, const rr_grads* out, void* stream,
-                  const float* dL_dmoments = nullptr, float dist_near = 0.f, float dist_far = 0.f);
+                  const float* dL_dmoments = nullptr, float dist_near = 0.f, float dist_far = 0.f,
+                  const rr_camera_grads* cg = nullptr);
 
 }  // namespace
 
@@ -660,6 +661,9 @@ size_t rr_binning_bytes(int num_rendered, int width, int height) {
     return carve_bin(nullptr, num_rendered, width, height).total;
 }
 size_t rr_backward_workspace_bytes(int P) { return align_up((size_t)std::max(P, 1) * GACC_STRIDE * sizeof(float)); }
+size_t rr_camera_grad_scratch_bytes(int P) {
+    return align_up((size_t)cam_grad_rows(std::max(P, 0)) * kCamGradRow * sizeof(float));
+}
 
 int rr_forward_geometry(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, int* radii, void* geom_buffer,
                         size_t geom_bytes, void* image_buffer, size_t image_bytes, int* num_rendered,
@@ -748,6 +752,14 @@ int rr_backward_aux(const rr_frame* f, const rr_camera* cam, const rr_gaussians*
                          dL_dalpha, nullptr, workspace, workspace_bytes, out, stream);
 }
 
+int rr_backward_camera(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
+                       const void* geom_buffer, const void* image_buffer, const void* binning_buffer, int num_rendered,
+                       const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha, void* workspace,
+                       size_t workspace_bytes, const rr_grads* out, const rr_camera_grads* cg, void* stream) {
+    return backward_impl(f, cam, g, radii, geom_buffer, image_buffer, binning_buffer, num_rendered, dL_dpix, dL_ddepth,
+                         dL_dalpha, nullptr, workspace, workspace_bytes, out, stream, nullptr, 0.f, 0.f, cg);
+}
+
 int rr_backward_aux_normal(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
                            const void* geom_buffer, const void* image_buffer, const void* binning_buffer,
                            int num_rendered, const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha,
@@ -792,13 +804,33 @@ int backward_impl(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g
                   const void* geom_buffer, const void* image_buffer, const void* binning_buffer, int num_rendered,
                   const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha, const float* dL_dnormal,
                   void* workspace, size_t workspace_bytes, const rr_grads* out, void* stream, const float* dL_dmoments,
-                  float dist_near, float dist_far) {
+                  float dist_near, float dist_far, const rr_camera_grads* cg) {
     int rc = validate(f, cam, g, false);
     if (rc) return rc;
     if (dL_dmoments && !dist_range_ok(dist_near, dist_far))
         return fail(RR_ERR_ARG, "dist_near / dist_far must be 0 < near < far, or both 0 (metric depth)");
     const int P = f->P, W = f->width, H = f->height, L = num_rendered;
-    if (P == 0) return RR_OK;
+    if (cg) {  // camera gradients (rr_backward_camera): every refusal before any device work
+        if (!cg->dL_dviewmatrix || !cg->dL_dprojmatrix || !cg->dL_dcampos)
+            return fail(RR_ERR_ARG, "rr_camera_grads: null gradient output");
+        if (!cg->scratch || ((uintptr_t)cg->scratch & 15u) != 0)
+            return fail(RR_ERR_ARG, "rr_camera_grads: scratch is null or not 16-byte aligned");
+        if (dL_dnormal || dL_dmoments)
+            return fail(RR_ERR_ARG, "camera gradients do not combine with dL_dnormal / dL_dmoments yet");
+        if (out && (out->adam || out->next))
+            return fail(RR_ERR_ARG, "camera gradients do not combine with rr_grads.adam / rr_grads.next");
+        if (cg->scratch_bytes < rr_camera_grad_scratch_bytes(P))
+            return fail(RR_ERR_CAPACITY, "rr_camera_grads: scratch too small");
+    }
+    if (P == 0) {
+        if (cg) {  // nothing rendered: the three arrays are zeros
+            hipStream_t st0 = (hipStream_t)stream;
+            RR_CHECK(hipMemsetAsync(cg->dL_dviewmatrix, 0, 16 * sizeof(float), st0), "camera gradients");
+            RR_CHECK(hipMemsetAsync(cg->dL_dprojmatrix, 0, 16 * sizeof(float), st0), "camera gradients");
+            RR_CHECK(hipMemsetAsync(cg->dL_dcampos, 0, 3 * sizeof(float), st0), "camera gradients");
+        }
+        return RR_OK;
+    }
     const bool aux = dL_ddepth || dL_dalpha || dL_dnormal || dL_dmoments;
     if (!out || (!dL_dpix && !aux) || !radii || !geom_buffer || !image_buffer || !workspace)
         return fail(RR_ERR_ARG, "null buffer");
@@ -865,7 +897,10 @@ int backward_impl(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g
             a.next = n;
             a.has_next = 1;
         }
-        if (dL_dnormal) launch_gauss_bwd_normal(a, st);
+        if (cg)
+            launch_gauss_bwd_cam(a, static_cast<float*>(cg->scratch), cg->dL_dviewmatrix, cg->dL_dprojmatrix,
+                                 cg->dL_dcampos, st);
+        else if (dL_dnormal) launch_gauss_bwd_normal(a, st);
         else if (aux) launch_gauss_bwd_depth(a, st);
         else launch_gauss_bwd(a, st);
     }

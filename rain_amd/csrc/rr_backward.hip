@@ -205,6 +205,20 @@ __device__ __forceinline__ void adam_small(const GaussBwdArgs& a, int idx, const
     }
 }
 
+// The 27 per-Gaussian terms of the camera gradients (include/rain_raster.h rr_backward_camera), with
+// the matrices in their memory layout m[4r + c] (x' = m0 x + m4 y + m8 z + m12: row r multiplies
+// component r of (mean, 1), column c is the output coordinate):
+//   v[3r + c]       c < 3   dL/dviewmatrix[4r + c]: dL/dt_c (mean, 1)_r, and for r < 3 the 3x3 block's
+//                           part of T = J W, (J^T dL/dT)[c][r]
+//   v[12 + 3r + k]  k < 3   dL/dprojmatrix[4r + c], c = (0, 1, 3)[k]: dL/dp_hom_c (mean, 1)_r
+//   v[24 + i]       i < 3   dL/dcampos[i] = -dL/d(mean - campos)_i of the SH view direction
+// Column 3 of the view matrix and column 2 of the projection (the z row) are read by no kernel.
+constexpr int kCamVals = 27;
+constexpr int kCamRow = kCamGradRow;  // floats per workgroup row of the partials array (k_cam_grad_reduce)
+struct CamPartials {
+    float v[kCamVals];
+};
+
 // What the per-Gaussian backward needs of one view: its camera, and the Gaussian's accumulators
 // from that view's blend backward (GACC layout: dmean2D.xy, dconic.xyz, dopacity, dcolor.rgb) with
 // its radius.
@@ -226,9 +240,12 @@ __device__ __forceinline__ ViewCam view_cam(const GaussBwdArgs& a) {
 // AUX 2 (k_gauss_bwd_normal): slots 10..12 hold dL/dn, the gradient of the view-space unit normal
 // n = s V R[:, k] / |V R[:, k]| (gaussian_normal_parts); the axis k and the sign s are constants of
 // the forward, so it reaches the rotation only, and joins dL/dq before the raw-mode normalisation.
-template <int DEG, bool PACKED, int AUX = 0>
+// CAM (k_gauss_bwd_cam): this Gaussian's terms of the camera gradients go to cam_out (CamPartials above;
+// left untouched, i.e. zero, for a Gaussian with radius <= 0).
+template <int DEG, bool PACKED, int AUX = 0, bool CAM = false>
 __device__ __forceinline__ void gauss_bwd_one(const GaussBwdArgs& a, const ViewCam& c, int idx, const GaccRec& rec,
-                                              const float* coef, float* gsh, bool acc_sh, SmallGrads& sg) {
+                                              const float* coef, float* gsh, bool acc_sh, SmallGrads& sg,
+                                              CamPartials* cam_out = nullptr) {
     const int M = a.M;
     float* dmean2 = a.dL_dmeans2D ? a.dL_dmeans2D + 3 * (size_t)idx : nullptr;
     float* dcol = a.dL_dcolors ? a.dL_dcolors + 3 * (size_t)idx : nullptr;
@@ -420,6 +437,11 @@ __device__ __forceinline__ void gauss_bwd_one(const GaussBwdArgs& a, const ViewC
         dmean.x += ((+sum2 - v.x * v.x) * dL_ddir.x - v.y * v.x * dL_ddir.y - v.z * v.x * dL_ddir.z) * invsum32;
         dmean.y += (-v.x * v.y * dL_ddir.x + (sum2 - v.y * v.y) * dL_ddir.y - v.z * v.y * dL_ddir.z) * invsum32;
         dmean.z += (-v.x * v.z * dL_ddir.x - v.y * v.z * dL_ddir.y + (sum2 - v.z * v.z) * dL_ddir.z) * invsum32;
+        if constexpr (CAM) {  // d(mean - campos) / dcampos = -1
+            cam_out->v[24] = -(((+sum2 - v.x * v.x) * dL_ddir.x - v.y * v.x * dL_ddir.y - v.z * v.x * dL_ddir.z) * invsum32);
+            cam_out->v[25] = -((-v.x * v.y * dL_ddir.x + (sum2 - v.y * v.y) * dL_ddir.y - v.z * v.y * dL_ddir.z) * invsum32);
+            cam_out->v[26] = -((-v.x * v.z * dL_ddir.x - v.y * v.z * dL_ddir.y + (sum2 - v.z * v.z) * dL_ddir.z) * invsum32);
+        }
     } else if (gsh && !acc_sh) {
         for (int i = 0; i < 3 * M; i++) gsh[i] = 0.f;
     }
@@ -427,6 +449,32 @@ __device__ __forceinline__ void gauss_bwd_one(const GaussBwdArgs& a, const ViewC
         dmean.x = __builtin_fmaf(g9, c.view[2], dmean.x);
         dmean.y = __builtin_fmaf(g9, c.view[6], dmean.y);
         dmean.z = __builtin_fmaf(g9, c.view[10], dmean.z);
+    }
+    if constexpr (CAM) {
+        const float mh[4] = {mean.x, mean.y, mean.z, 1.f};
+        // view: t = (mean, 1) . view feeds J (the clamped coordinates are constants, as above) and,
+        // through t.z, the depth map (slot 9) ...
+        const float dt[3] = {dL_dtx, dL_dty, dL_dtz + g9};
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+#pragma unroll
+            for (int k = 0; k < 3; k++) cam_out->v[3 * r + k] = mh[r] * dt[k];
+        // ... and its 3x3 block is W of T = J W: T[i][j] = sum_k J[i][k] view[4j + k]
+        const float J00 = c.focal_x * tz, J11 = c.focal_y * tz;
+        const float J02 = -(c.focal_x * t.x) * tz2, J12 = -(c.focal_y * t.y) * tz2;
+        const float dT0[3] = {dL_dT00, dL_dT01, dL_dT02}, dT1[3] = {dL_dT10, dL_dT11, dL_dT12};
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            cam_out->v[3 * j + 0] += J00 * dT0[j];
+            cam_out->v[3 * j + 1] += J11 * dT1[j];
+            cam_out->v[3 * j + 2] += J02 * dT0[j] + J12 * dT1[j];
+        }
+        // proj: mean2D = p_hom.xy / (p_hom.w + 1e-7), p_hom = (mean, 1) . proj
+        const float dph[3] = {dm2x * m_w, dm2y * m_w, -(mul1 * dm2x + mul2 * dm2y)};
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+#pragma unroll
+            for (int k = 0; k < 3; k++) cam_out->v[12 + 3 * r + k] = mh[r] * dph[k];
     }
     emit3(a.dL_dmeans3D, 0, dmean);
 
@@ -534,9 +582,13 @@ constexpr int kShStride = 49;
 // (11 small-group values) and into s_gr (the SH gradients; s_sh keeps the coefficients), then
 // scaled by va->grad_scale (1/N, rounded like grad.mul_(1/N)) before the Adam step.
 struct GaussBwdViewsArgs;
-template <int DEG, bool MULTI, int KGB, int AUX = 0>
+// CAM (k_gauss_bwd_cam, single view): the workgroup's sums of the 27 camera terms go to row
+// blockIdx.x of cam_partials ([workgroups][kCamRow]; entries 27..31 are written as zeros) through
+// s_cam, an LDS array of (KGB / 64) x kCamStride floats of its own.
+constexpr int kCamStride = 28;
+template <int DEG, bool MULTI, int KGB, int AUX = 0, bool CAM = false>
 __device__ __forceinline__ void gauss_bwd_block(const GaussBwdArgs& a, const GaussBwdViewsArgs* va, float* s_sh,
-                                                float* s_gr);
+                                                float* s_gr, float* s_cam = nullptr, float* cam_partials = nullptr);
 
 template <int DEG>
 // Occupancy: 3 waves per SIMD, set by LDS (a 196-B coefficient row per Gaussian, 12.5 KiB per
@@ -560,6 +612,60 @@ __global__ __launch_bounds__(kGB1) void k_gauss_bwd_normal(GaussBwdArgs a) {
     gauss_bwd_block<DEG, false, kGB1, 2>(a, nullptr, s_sh, s_sh);
 }
 
+// The camera-gradient variant (launch_gauss_bwd_cam): the depth / alpha kernel (slot 9 is zero when
+// the blend backward ran without a depth or alpha gradient) plus the per-workgroup camera partials.
+// LDS 50,672 B: three workgroups per CU as before; asked for three waves per SIMD the compiler fits
+// degree 3 into 160 VGPRs without scratch (190 and two waves left to itself).
+template <int DEG>
+__global__ __launch_bounds__(kGB1) __attribute__((amdgpu_waves_per_eu(3))) void k_gauss_bwd_cam(
+    GaussBwdArgs a, float* cam_partials) {
+    __shared__ float s_sh[kGB1 * kShStride];
+    __shared__ float s_cam[(kGB1 / 64) * kCamStride];
+    gauss_bwd_block<DEG, false, kGB1, 1, true>(a, nullptr, s_sh, s_sh, s_cam, cam_partials);
+}
+
+// Final pass of the camera gradients: one workgroup sums the rows of partials [nrows][kCamRow] in a
+// fixed order with double accumulators (thread (g, c): rows g, g + 32, ... of column c one after the
+// other, then g = 0..31 in order), and writes dL/dviewmatrix [16], dL/dprojmatrix [16] and
+// dL/dcampos [3] completely.  The rows are loaded sixteen at a time before they are added: a thread's
+// chain is latency-bound (one load per add took 0.15 ms at 3907 rows with 8 row groups).
+constexpr int kCamRedGroups = 32;  // row groups: 1024 threads
+constexpr int kCamRedBatch = 16;   // loads in flight per thread
+__global__ __launch_bounds__(kCamRedGroups* kCamRow) void k_cam_grad_reduce(const float* __restrict__ partials,
+                                                                            int nrows, float* __restrict__ d_view,
+                                                                            float* __restrict__ d_proj,
+                                                                            float* __restrict__ d_campos) {
+    __shared__ double s_acc[kCamRedGroups][kCamRow];
+    const int t = threadIdx.x, col = t & (kCamRow - 1), g = t / kCamRow;
+    double acc = 0.0;
+    for (int r0 = g; r0 < nrows; r0 += kCamRedGroups * kCamRedBatch) {
+        float v[kCamRedBatch];
+#pragma unroll
+        for (int k = 0; k < kCamRedBatch; k++) {
+            const int r = r0 + k * kCamRedGroups;
+            v[k] = r < nrows ? partials[(size_t)r * kCamRow + col] : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < kCamRedBatch; k++) acc += (double)v[k];
+    }
+    s_acc[g][col] = acc;
+    __syncthreads();
+    if (t < kCamRow) {
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < kCamRedGroups; k++) s += s_acc[k][t];
+        s_acc[0][t] = s;
+    }
+    __syncthreads();
+    if (t < 16) {
+        const int r = t >> 2, c = t & 3;
+        d_view[t] = c < 3 ? (float)s_acc[0][3 * r + c] : 0.f;
+        d_proj[t] = c != 2 ? (float)s_acc[0][12 + 3 * r + (c == 3 ? 2 : c)] : 0.f;
+    } else if (t < 19) {
+        d_campos[t - 16] = (float)s_acc[0][24 + (t - 16)];
+    }
+}
+
 constexpr int kMaxViews = 16;
 constexpr int kRecFloats = 10;  // packed accumulator record: GACC slots 0..8, radius (as a float)
 struct GaussBwdViewsArgs {
@@ -578,9 +684,10 @@ __global__ __launch_bounds__(kGB) void k_gauss_bwd_views(GaussBwdViewsArgs va) {
     gauss_bwd_block<DEG, true, kGB>(va.g, &va, s_sh, s_gr);
 }
 
-template <int DEG, bool MULTI, int KGB, int AUX>
+template <int DEG, bool MULTI, int KGB, int AUX, bool CAM>
 __device__ __forceinline__ void gauss_bwd_block(const GaussBwdArgs& a, const GaussBwdViewsArgs* va, float* s_sh,
-                                                float* s_gr) {
+                                                float* s_gr, float* s_cam, float* cam_partials) {
+    static_assert(!(CAM && MULTI), "camera gradients: single view only");
     const int t = threadIdx.x, lane = t & 63;
     const int i0 = blockIdx.x * KGB;
     const int nvalid = min(KGB, a.P - i0);
@@ -640,13 +747,17 @@ __device__ __forceinline__ void gauss_bwd_block(const GaussBwdArgs& a, const Gau
     }
     __syncthreads();
     SmallGrads upd;  // the small groups' parameters after the fused Adam step (rr_next_frame)
+    [[maybe_unused]] CamPartials cp;  // zero for the lanes past the last Gaussian and the invisible ones
+    if constexpr (CAM)
+#pragma unroll
+        for (int k = 0; k < kCamVals; k++) cp.v[k] = 0.f;
     if (t < nvalid) {
         SmallGrads sg;
         const int idx = i0 + t;
         float* row = stage ? s_sh + t * kShStride : nullptr;
         if (!MULTI) {
             const GaccRec rec{a.gacc + (size_t)idx * GACC_STRIDE, a.radii[idx], nullptr};
-            gauss_bwd_one<DEG, false, AUX>(a, view_cam(a), idx, rec, row, row, false, sg);
+            gauss_bwd_one<DEG, false, AUX, CAM>(a, view_cam(a), idx, rec, row, row, false, sg, CAM ? &cp : nullptr);
         } else {
             float* grow = stage ? s_gr + t * kShStride : nullptr;
             // each view's 40-B record is loaded while the previous view is processed (one record
@@ -675,7 +786,26 @@ __device__ __forceinline__ void gauss_bwd_block(const GaussBwdArgs& a, const Gau
         }
         if (a.use_adam) adam_small(a, i0 + t, sg, upd);
     }
+    if constexpr (CAM) {  // every lane of the wave: three cross-lane sums of nine, no LDS round trip per value
+        float* w = s_cam + (t >> 6) * kCamStride;
+#pragma unroll
+        for (int p = 0; p < 3; p++) {
+            float t0, t1, t2;
+            wave_sum9(cp.v[9 * p], cp.v[9 * p + 1], cp.v[9 * p + 2], cp.v[9 * p + 3], cp.v[9 * p + 4], cp.v[9 * p + 5],
+                      cp.v[9 * p + 6], cp.v[9 * p + 7], cp.v[9 * p + 8], t0, t1, t2);
+            red9_store(w + 9 * p, lane, t0, t1, t2);
+        }
+    }
     __syncthreads();
+    if constexpr (CAM) {  // the waves in order; one row per workgroup, no atomics
+        if (t < kCamRow) {
+            float s = 0.f;
+            if (t < kCamVals)
+#pragma unroll
+                for (int k = 0; k < KGB / 64; k++) s += s_cam[k * kCamStride + t];
+            cam_partials[(size_t)blockIdx.x * kCamRow + t] = s;
+        }
+    }
     // the next frame's preprocess reads the updated SH coefficients back from the LDS rows
     const bool back = !MULTI && a.has_next;
     if (stage && (a.dL_dsh || a.use_adam)) {
@@ -953,5 +1083,22 @@ static void launch_gauss_bwd_impl(const GaussBwdArgs& a, hipStream_t st) {
 void launch_gauss_bwd(const GaussBwdArgs& a, hipStream_t st) { launch_gauss_bwd_impl<0>(a, st); }
 void launch_gauss_bwd_depth(const GaussBwdArgs& a, hipStream_t st) { launch_gauss_bwd_impl<1>(a, st); }
 void launch_gauss_bwd_normal(const GaussBwdArgs& a, hipStream_t st) { launch_gauss_bwd_impl<2>(a, st); }
+
+int cam_grad_rows(int P) { return P > 0 ? (P + kGB1 - 1) / kGB1 : 1; }
+
+void launch_gauss_bwd_cam(const GaussBwdArgs& a, float* partials, float* d_view, float* d_proj, float* d_campos,
+                          hipStream_t st) {
+    const int nb = cam_grad_rows(a.P);
+    if (a.P > 0) {
+        // a.M <= 16 is validated by the API; no fused step and no next frame here (rr_backward_camera)
+        switch (a.shs ? a.D : 0) {
+            case 0: k_gauss_bwd_cam<0><<<nb, kGB1, 0, st>>>(a, partials); break;
+            case 1: k_gauss_bwd_cam<1><<<nb, kGB1, 0, st>>>(a, partials); break;
+            case 2: k_gauss_bwd_cam<2><<<nb, kGB1, 0, st>>>(a, partials); break;
+            default: k_gauss_bwd_cam<3><<<nb, kGB1, 0, st>>>(a, partials); break;
+        }
+    }
+    k_cam_grad_reduce<<<1, kCamRedGroups * kCamRow, 0, st>>>(partials, a.P > 0 ? nb : 0, d_view, d_proj, d_campos);
+}
 
 }  // namespace rr

@@ -198,6 +198,16 @@ void launch_gauss_bwd_depth(const GaussBwdArgs& a, hipStream_t st);
 // normal: the accumulators come from launch_blend_bwd_normal — slot 9 as above, and slots 10..12,
 // dL/d(view-space unit normal), are chained into dL/drotations (a.scales / a.rotations required).
 void launch_gauss_bwd_normal(const GaussBwdArgs& a, hipStream_t st);
+// camera (rr_backward_camera): the depth variant plus the gradients of the camera arrays.  Every
+// workgroup leaves the sums of its Gaussians' 27 camera terms in its row of partials
+// ([cam_grad_rows(P)][kCamGradRow] floats, no pre-zeroing), and a one-workgroup pass sums the rows in a
+// fixed order in double into d_view [16], d_proj [16] and d_campos [3], all fully written (zeros for
+// P == 0, for the entries no kernel reads, and for d_campos without SH inputs).  a.use_adam and
+// a.has_next must be 0.
+constexpr int kCamGradRow = 32;
+int cam_grad_rows(int P);  // workgroups of the per-Gaussian backward, at least 1
+void launch_gauss_bwd_cam(const GaussBwdArgs& a, float* partials, float* d_view, float* d_proj, float* d_campos,
+                          hipStream_t st);
 
 void launch_preprocess(const PreArgs& a, hipStream_t st);
 // One launch preprocessing the same rows for up to kMaxPreViews views (the Gaussian-sharded step's

@@ -11,7 +11,9 @@ depth map and of the accumulated alpha, and ``accumulated_alpha`` returns that a
 (include/rain_raster.h rr_backward_aux, rr_render_alpha); ``rasterize_gaussians_backward_normal``
 takes a gradient of the aux normal map of ``rasterize_gaussians_aux`` as well (rr_backward_aux_normal);
 ``rasterize_gaussians_dist`` also renders the depth-moment maps of the distortion loss and
-``rasterize_gaussians_backward_dist`` takes their gradient (rr_forward_render_dist, rr_backward_aux_dist).
+``rasterize_gaussians_backward_dist`` takes their gradient (rr_forward_render_dist, rr_backward_aux_dist);
+``rasterize_gaussians_backward_camera`` is ``rasterize_gaussians_backward_depth`` that also returns the
+gradients of the camera arrays (viewmatrix, projmatrix, campos; rr_backward_camera).
 
 Differences that are deliberate and invisible to callers: scratch buffers are sized by the C
 ABI's *_bytes() queries instead of grown through std::function callbacks; outputs the kernels
@@ -189,6 +191,21 @@ def rasterize_gaussians_backward_depth(background, means3D, radii, colors, scale
                      binningBuffer, imageBuffer, debug, low_pass, dL_dout_depth, dL_dout_alpha)
 
 
+def rasterize_gaussians_backward_camera(background, means3D, radii, colors, scales, rotations, scale_modifier,
+                                        cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh,
+                                        degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, low_pass,
+                                        dL_dout_depth, dL_dout_alpha):
+    """rasterize_gaussians_backward_depth plus the gradients of the camera arrays (rr_backward_camera):
+    returns its 8 tensors and (d_viewmatrix [4,4], d_projmatrix [4,4], d_campos [3]), the gradients of
+    `viewmatrix`, `projmatrix` and `campos` as three independent inputs, in their memory layout.  The
+    view matrix is reached through the EWA Jacobian, its 3x3 block and the view depth of the depth map;
+    the projection through means2D (its z row gets 0); campos through the SH view direction (0 with
+    precomputed colours).  The depth and alpha gradients may both be empty (a colour-only loss)."""
+    return _backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
+                     viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R,
+                     binningBuffer, imageBuffer, debug, low_pass, dL_dout_depth, dL_dout_alpha, camera=True)
+
+
 def rasterize_gaussians_backward_normal(background, means3D, radii, colors, scales, rotations, scale_modifier,
                                         cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh,
                                         degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, low_pass,
@@ -229,7 +246,7 @@ def _present(t):
 def _backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
               projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
               imageBuffer, debug, low_pass, dL_dout_depth, dL_dout_alpha, dL_dout_normal=None, dL_dout_moments=None,
-              dist=(0.0, 0.0)):
+              dist=(0.0, 0.0), camera=False):
     P = means3D.size(0)
     nrm = _present(dL_dout_normal)
     mom = _present(dL_dout_moments)
@@ -250,7 +267,8 @@ def _backward(background, means3D, radii, colors, scales, rotations, scale_modif
     fopts = dict(dtype=torch.float32, device=device)
     if P == 0:
         z = lambda *s: torch.zeros(s, **fopts)  # noqa: E731
-        return (z(0, 3), z(0, NUM_CHANNELS), z(0, 1), z(0, 3), z(0, 6), z(0, M, 3), z(0, 3), z(0, 4))
+        return (z(0, 3), z(0, NUM_CHANNELS), z(0, 1), z(0, 3), z(0, 6), z(0, M, 3), z(0, 3), z(0, 4)) + \
+            ((z(4, 4), z(4, 4), z(3)) if camera else ())
     L = N.raster()
     keep = dict(
         bg=_dev_f32(background, device, "bg"), means3D=_dev_f32(means3D, device, "means3D"),
@@ -278,6 +296,20 @@ def _backward(background, means3D, radii, colors, scales, rotations, scale_modif
                                                "dL_dcov3D", "dL_dsh", "dL_dscales", "dL_drotations")])
     ws = torch.empty((L.rr_backward_workspace_bytes(P),), dtype=torch.uint8, device=device)
     stream = N.stream_of(means3D)
+    res = (out["dL_dmeans2D"], out["dL_dcolors"], out["dL_dopacity"], out["dL_dmeans3D"], out["dL_dcov3D"],
+           out["dL_dsh"], out["dL_dscales"], out["dL_drotations"])
+    if camera:
+        if nrm or mom:
+            raise RuntimeError("camera gradients do not combine with dL_dout_normal / dL_dout_moments yet")
+        d_view, d_proj, d_campos = torch.empty((4, 4), **fopts), torch.empty((4, 4), **fopts), torch.empty((3,), **fopts)
+        scratch = torch.empty((L.rr_camera_grad_scratch_bytes(P),), dtype=torch.uint8, device=device)
+        cg = N.RRCameraGrads(_ptr(d_view), _ptr(d_proj), _ptr(d_campos), _ptr(scratch), scratch.numel())
+        N.check(L.rr_backward_camera(ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs), _ptr(keep["radii"]),
+                                     _ptr(geomBuffer), _ptr(imageBuffer), _ptr(binningBuffer), int(R),
+                                     _ptr(keep["dpix"]), _ptr(keep["ddepth"]), _ptr(keep["dalpha"]), _ptr(ws),
+                                     ws.numel(), ctypes.byref(grads), ctypes.byref(cg), stream),
+                "rasterize_gaussians_backward_camera")
+        return res + (d_view, d_proj, d_campos)
     if mom:
         N.check(L.rr_backward_aux_dist(ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs), _ptr(keep["radii"]),
                                        _ptr(geomBuffer), _ptr(imageBuffer), _ptr(binningBuffer), int(R),

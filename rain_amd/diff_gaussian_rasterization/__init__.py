@@ -138,6 +138,57 @@ class _RasterizeGaussiansDepth(torch.autograd.Function):
         return d_means3D, d_means2D, d_sh, d_colors, d_opacities, d_scales, d_rotations, d_cov3D, None
 
 
+class _RasterizeGaussiansCamera(torch.autograd.Function):
+    """_RasterizeGaussiansDepth with the camera as a differentiable input (no reference counterpart;
+    GaussianRasterizer.forward_camera): viewmatrix, projmatrix and campos of the settings are also passed
+    as tensor inputs, three independent ones, and receive the gradients of
+    _C.rasterize_gaussians_backward_camera.  Returns (color, radii, depth, alpha)."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                raster_settings, viewmatrix, projmatrix, campos):
+        # the kernels read contiguous fp32 arrays; the gradients come back in that layout
+        viewmatrix, projmatrix, campos = (t.detach().to(torch.float32).contiguous()
+                                          for t in (viewmatrix, projmatrix, campos))
+        ctx.cam_shapes = (viewmatrix.shape, projmatrix.shape, campos.shape)
+        s = raster_settings._replace(viewmatrix=viewmatrix, projmatrix=projmatrix, campos=campos)
+        args = _forward_args(s, means3D, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, sh)
+        num_rendered, color, radii, depth, geom, binning, img = _invoke(
+            _C.rasterize_gaussians, args, s.debug, "snapshot_fw.dump",
+            "\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
+        alpha = _C.accumulated_alpha(img, s.image_height, s.image_width)
+        ctx.raster_settings = s
+        ctx.num_rendered = num_rendered
+        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning,
+                              img)
+        ctx.mark_non_differentiable(radii)
+        ctx.set_materialize_grads(False)
+        return color, radii, depth, alpha
+
+    @staticmethod
+    def backward(ctx, grad_out_color, grad_radii, grad_depth, grad_alpha):
+        if grad_out_color is None and grad_depth is None and grad_alpha is None:
+            return (None,) * 12
+        s = ctx.raster_settings
+        empty = torch.Tensor([])  # "absent" (a NULL pointer in the library)
+        grad_out_color, grad_depth, grad_alpha = (empty if g is None else g
+                                                  for g in (grad_out_color, grad_depth, grad_alpha))
+        args = _backward_args(s, ctx.saved_tensors, ctx.num_rendered, grad_out_color) + (grad_depth, grad_alpha)
+        if not any(ctx.needs_input_grad[9:12]):  # a fixed camera: the plain depth backward
+            d_means2D, d_colors, d_opacities, d_means3D, d_cov3D, d_sh, d_scales, d_rotations = _invoke(
+                _C.rasterize_gaussians_backward_depth, args, s.debug, "snapshot_bw.dump",
+                "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
+            d_view = d_proj = d_campos = None
+        else:
+            (d_means2D, d_colors, d_opacities, d_means3D, d_cov3D, d_sh, d_scales, d_rotations, d_view, d_proj,
+             d_campos) = _invoke(_C.rasterize_gaussians_backward_camera, args, s.debug, "snapshot_bw.dump",
+                                 "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
+            # (in the inputs' own shapes: a flat [16] matrix gets a flat gradient)
+            d_view, d_proj, d_campos = (g.view(sh) for g, sh in zip((d_view, d_proj, d_campos), ctx.cam_shapes))
+        return (d_means3D, d_means2D, d_sh, d_colors, d_opacities, d_scales, d_rotations, d_cov3D, None, d_view,
+                d_proj, d_campos)
+
+
 class _RasterizeGaussiansNormal(torch.autograd.Function):
     """_RasterizeGaussiansDepth plus a differentiable aux normal map (no reference counterpart;
     GaussianRasterizer.forward_normal): returns (color, radii, depth, alpha, normal) with
@@ -269,6 +320,22 @@ class GaussianRasterizer(nn.Module):
         return _RasterizeGaussiansDepth.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                               cov3D_precomp, self.raster_settings)
 
+    def forward_camera(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
+                       cov3D_precomp=None):
+        """forward_depth() with a differentiable camera (opt-in; pose refinement, tracking): the same
+        (color [3,H,W], radii [P], depth [1,H,W], alpha [1,H,W]), and autograd delivers the gradients of
+        raster_settings.viewmatrix / projmatrix / campos — three independent inputs, each in its memory
+        layout — to whatever produced those tensors (rain_amd.cameras.CameraPose).  The view matrix is
+        reached through the EWA Jacobian, its 3x3 block and the view depth of the depth map; the
+        projection through means2D only (its z row gets 0); campos through the SH view direction (0
+        with colors_precomp).  Culling, radii and the depth order are discrete and contribute nothing."""
+        _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp)
+        shs, colors_precomp, scales, rotations, cov3D_precomp = _absent_as_empty(shs, colors_precomp, scales,
+                                                                                 rotations, cov3D_precomp)
+        s = self.raster_settings
+        return _RasterizeGaussiansCamera.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+                                               cov3D_precomp, s, s.viewmatrix, s.projmatrix, s.campos)
+
     def forward_normal(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                        cov3D_precomp=None):
         """forward_depth() plus a differentiable aux normal map (opt-in): returns (color [3,H,W],
@@ -322,4 +389,4 @@ class GaussianRasterizer(nn.Module):
 
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "_RasterizeGaussians",
-           "_RasterizeGaussiansDepth", "_RasterizeGaussiansNormal", "_RasterizeGaussiansDist", "_C"]
+           "_RasterizeGaussiansDepth", "_RasterizeGaussiansCamera", "_RasterizeGaussiansNormal", "_RasterizeGaussiansDist", "_C"]

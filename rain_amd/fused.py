@@ -268,7 +268,8 @@ def forward_next(nxt: NextFrame, model, cache: BinningCache | None = None):
 def backward(st: RawFrame, dL_dpix: torch.Tensor, grads: dict | None, stats: tuple | None = None,
              adam: "N.RRAdam | None" = None, dmeans2D: torch.Tensor | None = None, next_frame: NextFrame | None = None,
              dL_ddepth: torch.Tensor | None = None, dL_dalpha: torch.Tensor | None = None,
-             dL_dnormal: torch.Tensor | None = None, dL_dmoments: torch.Tensor | None = None):
+             dL_dnormal: torch.Tensor | None = None, dL_dmoments: torch.Tensor | None = None,
+             cam_grads: tuple | None = None):
     """Write dLoss/d(raw parameter) into grads['xyz'|'f_dc'|'f_rest'|'opacity'|'scaling'|'rotation']
     (contiguous fp32 tensors of the parameter shapes, fully overwritten) and, if `stats` =
     (grad_accum [P,1], denom [P,1], max_radii2D [P]) is given, update the densification statistics
@@ -287,8 +288,24 @@ def backward(st: RawFrame, dL_dpix: torch.Tensor, grads: dict | None, stats: tup
     and everything else through alpha_i.
     `dL_dmoments` ([2,H,W] fp32, optional): gradient of the depth-moment maps of a frame rendered with
     forward(dist=(near, far)), added likewise (rr_backward_aux_dist, with the frame's near / far): it
-    reaches xyz through the view depth and everything else through alpha_i."""
+    reaches xyz through the view depth and everything else through alpha_i.
+    `cam_grads` = (d_viewmatrix [4,4], d_projmatrix [4,4], d_campos [3]) (contiguous fp32, optional): they
+    receive the gradients of the frame's three camera arrays (rr_backward_camera), fully overwritten.
+    Colour, depth and alpha gradients only, and no `adam` / `next_frame`."""
+    if cam_grads is not None:
+        if dL_dnormal is not None or dL_dmoments is not None:
+            raise RuntimeError("rain_amd.fused.backward: camera gradients do not combine with dL_dnormal / "
+                               "dL_dmoments yet")
+        if adam is not None or next_frame is not None:
+            raise RuntimeError("rain_amd.fused.backward: camera gradients do not combine with the fused optimizer "
+                               "step / the next frame")
+        for t, shape in zip(cam_grads, ((4, 4), (4, 4), (3,))):
+            if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise RuntimeError("rain_amd.fused: cam_grads must be contiguous float32 [4,4], [4,4], [3] tensors")
     if st.P == 0:
+        if cam_grads is not None:
+            for t in cam_grads:
+                t.zero_()
         return
     L = N.raster()
     aux = dL_ddepth is not None or dL_dalpha is not None or dL_dnormal is not None or dL_dmoments is not None
@@ -329,6 +346,15 @@ def backward(st: RawFrame, dL_dpix: torch.Tensor, grads: dict | None, stats: tup
         frame.flags |= N.RR_FLAG_WORKSPACE_REGISTERED
     else:
         ws = torch.empty((L.rr_backward_workspace_bytes(st.P),), dtype=torch.uint8, device=dev)
+    if cam_grads is not None:
+        scratch = torch.empty((L.rr_camera_grad_scratch_bytes(st.P),), dtype=torch.uint8, device=dev)
+        cg = N.RRCameraGrads(_p(cam_grads[0]), _p(cam_grads[1]), _p(cam_grads[2]), _p(scratch), scratch.numel())
+        N.check(L.rr_backward_camera(ctypes.byref(frame), ctypes.byref(st.cam), ctypes.byref(st.gs), _p(st.radii),
+                                     _p(st.geom), _p(st.img), _p(st.binning), st.num_rendered,
+                                     _p(dpix) if dL_dpix is not None else None, _p(maps[0]), _p(maps[1]), _p(ws),
+                                     ws.numel(), ctypes.byref(out), ctypes.byref(cg), N.stream_of(dpix)),
+                "fused backward (camera)")
+        return
     if maps[3] is not None:
         N.check(L.rr_backward_aux_dist(ctypes.byref(frame), ctypes.byref(st.cam), ctypes.byref(st.gs), _p(st.radii),
                                        _p(st.geom), _p(st.img), _p(st.binning), st.num_rendered,
@@ -449,6 +475,57 @@ class RasterizeRawParamsDepth(torch.autograd.Function):
         backward(st, grad_color, grads, dmeans2D=d2, dL_ddepth=grad_depth, dL_dalpha=grad_alpha)
         return (grads["xyz"], grads["f_dc"], grads["f_rest"], grads["opacity"], grads["scaling"], grads["rotation"], d2,
                 None, None, None, None, None, None, None, None, None, None, None)
+
+
+class RasterizeRawParamsCamera(torch.autograd.Function):
+    """RasterizeRawParamsDepth with the camera as a differentiable input (render(pose_grad=True)): the
+    same (color, radii, depth, alpha), and its backward also returns the gradients of `viewmatrix`,
+    `projmatrix` and `campos` — three independent inputs, each in its memory layout
+    (rr_backward_camera).  When none of the three requires a gradient the plain depth backward runs."""
+
+    @staticmethod
+    def forward(ctx, xyz, f_dc, f_rest, opacity, scaling, rotation, means2D, sh_degree, W, H, tanfovx, tanfovy,
+                viewmatrix, projmatrix, campos, bg, low_pass, scale_modifier):
+        viewmatrix, projmatrix, campos = (t.detach().to(torch.float32).contiguous()
+                                          for t in (viewmatrix, projmatrix, campos))
+        ctx.cam_shapes = (viewmatrix.shape, projmatrix.shape, campos.shape)
+        color, radii, depth, st = forward_params((xyz, f_dc, f_rest, opacity, scaling, rotation), sh_degree, W, H,
+                                                 tanfovx, tanfovy, viewmatrix, projmatrix, campos, bg, low_pass,
+                                                 scale_modifier)
+        alpha = accumulated_alpha(st)
+        keep, _p6 = st.keep
+        ctx.save_for_backward(xyz, f_dc, f_rest, opacity, scaling, rotation, st.radii, st.geom, st.img, st.binning,
+                              st.ws, *keep)
+        ctx.desc = (st.frame, st.cam, st.gs, st.num_rendered, st.P, st.M)
+        ctx.mark_non_differentiable(radii)
+        ctx.set_materialize_grads(False)
+        return color, radii, depth, alpha
+
+    @staticmethod
+    def backward(ctx, grad_color, _grad_radii, grad_depth, grad_alpha):
+        if grad_color is None and grad_depth is None and grad_alpha is None:
+            return (None,) * 18
+        xyz, f_dc, f_rest, opacity, scaling, rotation, radii, geom, img, binning, ws, *keep = ctx.saved_tensors
+        frame, cam, gs, num_rendered, P, M = ctx.desc
+        p = (xyz, f_dc, opacity, scaling, rotation, f_rest)  # kernel order
+        ws_first = ws if not getattr(ctx, "ws_used", False) else None
+        ctx.ws_used = True
+        st = RawFrame(frame, cam, gs, (tuple(keep), p), radii, geom, img, binning, num_rendered, P, M, ws_first)
+        grads = dict(xyz=torch.empty_like(p[0]), f_dc=torch.empty_like(p[1]), opacity=torch.empty_like(p[2]),
+                     scaling=torch.empty_like(p[3]), rotation=torch.empty_like(p[4]), f_rest=torch.empty_like(p[5]))
+        d2 = torch.empty((st.P, 3), dtype=torch.float32, device=p[0].device)
+        if st.P == 0:
+            d2.zero_()
+        cg = None
+        if any(ctx.needs_input_grad[12:15]):
+            fo = dict(dtype=torch.float32, device=p[0].device)
+            cg = (torch.empty((4, 4), **fo), torch.empty((4, 4), **fo), torch.empty((3,), **fo))
+        backward(st, grad_color, grads, dmeans2D=d2, dL_ddepth=grad_depth, dL_dalpha=grad_alpha, cam_grads=cg)
+        # (in the inputs' own shapes: a flat [16] matrix gets a flat gradient)
+        d_view, d_proj, d_campos = (g.view(s) for g, s in zip(cg, ctx.cam_shapes)) if cg is not None \
+            else (None, None, None)
+        return (grads["xyz"], grads["f_dc"], grads["f_rest"], grads["opacity"], grads["scaling"], grads["rotation"], d2,
+                None, None, None, None, None, d_view, d_proj, d_campos, None, None, None)
 
 
 class RasterizeRawParamsNormal(torch.autograd.Function):

@@ -69,13 +69,20 @@ class PipelineParams:
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
-           low_pass=0.3, depth_grad=False, normal_grad=False, dist_grad=False, dist_near=0.2, dist_far=100.0):
+           low_pass=0.3, depth_grad=False, normal_grad=False, dist_grad=False, dist_near=0.2, dist_far=100.0,
+           pose_grad=False):
     """The reference's render(); `depth_grad` adds a differentiable "depth" and "alpha" to the
     dictionary, `normal_grad` (which implies depth_grad) a differentiable aux "normal" map [3,H,W]
     as well (sum alpha_i T_i n_i, GaussianRasterizer.forward_normal).  `dist_grad` (which implies
     depth_grad and composes with normal_grad) adds the differentiable "depth_moments" [2,H,W] =
     (sum w m, sum w m^2) of the mapped depth m (NDC depth between dist_near and dist_far, or the metric
-    depth for 0, 0; GaussianRasterizer.forward_distortion) and "distortion" [1,H,W] = alpha M2 - M1^2."""
+    depth for 0, 0; GaussianRasterizer.forward_distortion) and "distortion" [1,H,W] = alpha M2 - M1^2.
+    `pose_grad` (which implies depth_grad; not with normal_grad / dist_grad yet) makes the camera a
+    differentiable input: the gradients of viewpoint_camera.world_view_transform, full_proj_transform
+    and camera_center reach whatever produced them (rain_amd.cameras.CameraPose;
+    GaussianRasterizer.forward_camera)."""
+    if pose_grad and (normal_grad or dist_grad):
+        raise Exception("render(pose_grad=True) does not combine with normal_grad / dist_grad yet")
     if normal_grad and pipe.compute_cov3D_python:
         raise Exception("render(normal_grad=True) needs the scale/rotation pair (not compute_cov3D_python): "
                         "normals come from the scale axes")
@@ -119,6 +126,12 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
             return {"render": rendered_image, "viewspace_points": screenspace_points,
                     "visibility_filter": radii > 0, "radii": radii, "depth": depth, "alpha": alpha,
                     "normal": normal}
+        if pose_grad:
+            from .fused import RasterizeRawParamsCamera
+
+            rendered_image, radii, depth, alpha = RasterizeRawParamsCamera.apply(*raw_args)
+            return {"render": rendered_image, "viewspace_points": screenspace_points,
+                    "visibility_filter": radii > 0, "radii": radii, "depth": depth, "alpha": alpha}
         if depth_grad:
             rendered_image, radii, depth, alpha = RasterizeRawParamsDepth.apply(*raw_args)
             return {"render": rendered_image, "viewspace_points": screenspace_points,
@@ -162,6 +175,12 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
             scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp)
         return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
                 "radii": radii, "depth": depth, "alpha": alpha, "normal": normal}
+    if pose_grad:
+        rendered_image, radii, depth, alpha = rasterizer.forward_camera(
+            means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors_precomp, opacities=opacity,
+            scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp)
+        return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
+                "radii": radii, "depth": depth, "alpha": alpha}
     if depth_grad:
         rendered_image, radii, depth, alpha = rasterizer.forward_depth(
             means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors_precomp, opacities=opacity,
