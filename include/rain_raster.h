@@ -382,6 +382,42 @@ int rr_backward_aux_dist(const rr_frame* f, const rr_camera* cam, const rr_gauss
 int rr_render_alpha(const rr_frame* f, const void* image_buffer, float* out_alpha, void* stream);
 
 /*
+ * ---- Per-Gaussian blend-contribution statistics (no reference counterpart; what importance pruning
+ * reads: LightGaussian's global significance, RadSplat's / Mini-Splatting's max-weight test, hit counts).
+ * For the frame last rendered into the given buffers (f: that frame, with the flags of the forward that
+ * filled them; radii: its radii), with the blend weight of Gaussian i at pixel p
+ *   w_i(p) = alpha_i(p) T_i(p),   T_i(p) = prod_{j in front of i, contributing at p} (1 - alpha_j(p)),
+ * where i contributes at p exactly when the forward blended it there (alpha >= 1/255, power <= 0, before
+ * the pixel saturated), rr_contributions produces one 16-byte record per Gaussian:
+ *   sum_w   sum_p w_i(p)
+ *   sum_gw  sum_p g(p) w_i(p), g = pixel_weight [H*W] (either sign; e.g. an error map or a mask), or
+ *           g == 1 everywhere when pixel_weight is NULL (then sum_gw is sum_w, up to the atomics' order)
+ *   max_w   max_p w_i(p), >= 0 (pixel_weight never enters it, nor count)
+ *   count   pixels where i contributed; 32 bits, it wraps past 2^32 hits when frames are accumulated
+ * It walks every tile's list (A-list then B-list of early-stop binning, the first tile_max pairs) front
+ * to back, recomputing alpha with the forward's arithmetic and T from 1, so the result does not depend
+ * on how the lists were split into phases.  max_w and count are deterministic (integer atomics: the max
+ * on the float's bits, valid because w >= 0); the two sums are float atomics, equal up to their order.
+ *   accumulate == 0: every record of out is written; Gaussians with radii <= 0, or contributing
+ *                    nowhere, get zeros.  A frame with P == 0, num_rendered == 0 or no binning buffer
+ *                    launches nothing that walks.
+ *   accumulate != 0: the frame is added into what out holds (sums add, max_w takes the max, counts
+ *                    add): N views cost N calls and no extra pass.
+ * No host synchronisation; everything runs on stream.  RR_ERR_ARG before any device work for: a null f
+ * or out; out not 16-byte aligned; P < 0, width / height <= 0, num_rendered < 0; with P > 0, null
+ * radii / geom_buffer / image_buffer.
+ */
+typedef struct rr_contrib {
+    float sum_w;    /* sum_p w_i(p) */
+    float sum_gw;   /* sum_p g(p) w_i(p); g == 1 everywhere if no map */
+    float max_w;    /* max_p w_i(p), >= 0 */
+    uint32_t count; /* pixels where i contributed */
+} rr_contrib;       /* [P], 16-B aligned */
+int rr_contributions(const rr_frame* f, const int* radii, const void* geom_buffer, const void* image_buffer,
+                     const void* binning_buffer, int num_rendered, const float* pixel_weight /* [H*W] or NULL */,
+                     int accumulate, rr_contrib* out /* [P] */, void* stream);
+
+/*
  * ---- Gaussian-sharded view-parallel training step (N ranks; no reference counterpart: the
  * reference is single-GPU).  Rank r owns the Gaussian rows
  * [r*Q, (r+1)*Q) (Q a multiple of 256, N*Q >= P) and renders one view per step; the bytes that

@@ -25,7 +25,7 @@ CXXFLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-W
 
 LIBS = {
     "librain_raster.so": ["rr_forward.hip", "rr_bin.hip", "rr_blend_fwd_s.hip", "rr_blend.hip", "rr_backward.hip",
-                          "rr_sort.hip", "rr_api.hip"],
+                          "rr_sort.hip", "rr_contrib.hip", "rr_api.hip"],
     "librain_loss.so": ["loss.hip", "geom_loss.hip"],
     "librain_knn.so": ["knn.hip"],
     "librain_train.so": ["train.hip", "densify.hip"],
@@ -58,6 +58,8 @@ EXTRA = {
     # below the blend (next to their use in the loop latch), serialising them again
     "rr_blend_fwd_s.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops", "-mllvm", "-disable-machine-sink"],
     "rr_blend.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"] + MAX_ILP,
+    # rr_contrib.hip: the blend backward's pair loop shape, so the same packed-fp32 setting
+    "rr_contrib.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "loss.hip": ["-mllvm", "-pragma-unroll-threshold=200000",
                  "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }

@@ -79,6 +79,13 @@ class RRCameraGrads(ctypes.Structure):
                 ("dL_dcampos", ctypes.c_void_p), ("scratch", ctypes.c_void_p), ("scratch_bytes", ctypes.c_size_t)]
 
 
+class RRContrib(ctypes.Structure):
+    """include/rain_raster.h rr_contrib: one Gaussian's blend-contribution record (16 B; the Python
+    layers view the [P] array as a [P,4] float32 tensor, count through its bits)."""
+    _fields_ = [("sum_w", ctypes.c_float), ("sum_gw", ctypes.c_float), ("max_w", ctypes.c_float),
+                ("count", ctypes.c_uint32)]
+
+
 class RRView(ctypes.Structure):
     _fields_ = [("viewmatrix", ctypes.c_void_p), ("projmatrix", ctypes.c_void_p), ("campos", ctypes.c_void_p),
                 ("tan_fovx", ctypes.c_float), ("tan_fovy", ctypes.c_float), ("low_pass", ctypes.c_float),
@@ -109,7 +116,7 @@ RASTER_SYMBOLS = ["rr_geometry_bytes", "rr_image_bytes", "rr_binning_bytes", "rr
                   "rr_backward_records", "rr_gauss_backward_views", "rr_set_forward_workspace",
                   "rr_backward_aux", "rr_render_alpha", "rr_backward_aux_normal",
                   "rr_forward_render_dist", "rr_backward_aux_dist",
-                  "rr_camera_grad_scratch_bytes", "rr_backward_camera"]
+                  "rr_camera_grad_scratch_bytes", "rr_backward_camera", "rr_contributions"]
 
 _raster = None
 _knn = None
@@ -170,6 +177,9 @@ def raster():
                                            ctypes.POINTER(RRGrads), vp]
         L.rr_render_alpha.restype = ci
         L.rr_render_alpha.argtypes = [fp, vp, vp, vp]
+        # frame, radii, geom, image, binning, num_rendered, pixel_weight, accumulate, out [P] rr_contrib, stream
+        L.rr_contributions.restype = ci
+        L.rr_contributions.argtypes = [fp, vp, vp, vp, vp, ci, vp, ci, vp, vp]
         L.rr_mark_visible.restype = ci
         L.rr_mark_visible.argtypes = [ci, vp, vp, vp, vp, vp]
         L.rr_last_error.restype = ctypes.c_char_p

@@ -16,6 +16,7 @@
 
 #include "../../include/rain_raster.h"
 #include "rr_common.hpp"
+#include "rr_contrib.hpp"
 #include "rr_kernels.hpp"
 #include "rr_layout.hpp"
 
@@ -794,6 +795,35 @@ int rr_render_alpha(const rr_frame* f, const void* image_buffer, float* out_alph
     const Img im = carve_img(const_cast<void*>(image_buffer), W, H);
     launch_render_alpha(im.final_T, n, out_alpha, st);
     return check(f, st, "render alpha");
+}
+
+int rr_contributions(const rr_frame* f, const int* radii, const void* geom_buffer, const void* image_buffer,
+                     const void* binning_buffer, int num_rendered, const float* pixel_weight, int accumulate,
+                     rr_contrib* out, void* stream) {
+    if (!f) return fail(RR_ERR_ARG, "null frame");
+    const int P = f->P, W = f->width, H = f->height;
+    if (P < 0 || W <= 0 || H <= 0) return fail(RR_ERR_ARG, "bad P / width / height");
+    if (num_rendered < 0) return fail(RR_ERR_ARG, "bad num_rendered");
+    if (!out) return fail(RR_ERR_ARG, "null output buffer");
+    if (((uintptr_t)out & 15u) != 0) return fail(RR_ERR_ARG, "out is not 16-byte aligned");
+    if (P == 0) return RR_OK;  // no records
+    if (!radii || !geom_buffer || !image_buffer) return fail(RR_ERR_ARG, "null buffer");
+    hipStream_t st = (hipStream_t)stream;
+    uint32_t* rec = reinterpret_cast<uint32_t*>(out);
+    if (!accumulate) launch_contrib_clear(rec, P, st);
+    // nothing visible, or a frame without pairs (it has no binning buffer): no list to walk
+    if (num_rendered > 0 && binning_buffer) {
+        const Geom gm = carve_geom(const_cast<void*>(geom_buffer), P);
+        const Img im = carve_img(const_cast<void*>(image_buffer), W, H);
+        const Bin bn = carve_bin(const_cast<void*>(binning_buffer), 0, W, H);  // point_list comes first
+        ContribArgs a{};
+        a.P = P; a.W = W; a.H = H; a.gx = grid_x(W); a.gy = grid_y(H);
+        a.ranges = im.ranges; a.ranges_b = im.ranges_b; a.point_list = bn.point_list; a.splats = gm.splats;
+        a.tile_max = im.tile_max; a.n_contrib = im.n_contrib; a.pixel_weight = pixel_weight;
+        a.out = rec;
+        launch_contrib(a, st);
+    }
+    return check(f, st, "contributions");
 }
 
 }  // extern "C"

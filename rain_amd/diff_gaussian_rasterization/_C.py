@@ -356,6 +356,43 @@ def accumulated_alpha(imageBuffer, H, W):
     return out
 
 
+def gaussian_contributions(radii, geomBuffer, binningBuffer, imageBuffer, num_rendered, P, W, H, pixel_weight=None,
+                           out=None):
+    """Per-Gaussian blend-contribution statistics of the frame last rendered into the buffers
+    (rasterize_gaussians' radii, geomBuffer, binningBuffer, imgBuffer and num_rendered;
+    include/rain_raster.h rr_contributions).  With w_i(p) = alpha_i(p) T_i(p) over the pixels the forward
+    blended Gaussian i into, returns (sum_w [P], sum_gw [P], max_w [P], count [P] int32): sum_p w, sum_p g w
+    with g = pixel_weight [H,W] (either sign; 1 everywhere when None), max_p w, and the number of pixels.
+    The four are views of one [P,4] float32 buffer (count through its bits; it wraps past 2^32 hits).
+    Passing `out`, such a [P,4] buffer, accumulates this frame into it (sums add, max_w takes the max,
+    counts add) and returns views of it.  No gradient flows; no CPU fallback."""
+    P, W, H = int(P), int(W), int(H)
+    device = _require_device(radii)
+    if out is None:
+        buf = torch.empty((P, 4), dtype=torch.float32, device=device)  # written completely
+    else:
+        buf = out
+        if buf.dtype != torch.float32 or tuple(buf.shape) != (P, 4) or not buf.is_contiguous() or buf.device != device:
+            raise RuntimeError(f"out must be a contiguous float32 [{P}, 4] tensor on {device}")
+    views = (buf[:, 0], buf[:, 1], buf[:, 2], buf.view(torch.int32)[:, 3])
+    if P == 0:
+        return views
+    g = _dev_f32(pixel_weight, device, "pixel_weight")
+    if g is not None and g.numel() != H * W:
+        raise RuntimeError(f"pixel_weight must have {H} x {W} elements (got {tuple(g.shape)})")
+    L = N.raster()
+    if radii.numel() != P or geomBuffer.numel() < L.rr_geometry_bytes(P) or \
+            imageBuffer.numel() < L.rr_image_bytes(W, H):
+        raise RuntimeError("gaussian_contributions: radii / buffers are not those of a P-Gaussian frame of this size")
+    radii = radii.contiguous()
+    frame = _frame(P, 0, 0, W, H, 1.0, 1.0, 1.0, 0.3, False, False)
+    N.check(L.rr_contributions(ctypes.byref(frame), _ptr(radii), _ptr(geomBuffer), _ptr(imageBuffer),
+                                        _ptr(binningBuffer), int(num_rendered), _ptr(g), 0 if out is None else 1,
+                                        _ptr(buf), N.stream_of(radii)),
+            "gaussian_contributions")
+    return views
+
+
 def mark_visible(means3D, viewmatrix, projmatrix):
     P = means3D.size(0)
     device = _require_device(means3D)

@@ -110,6 +110,12 @@ class OptimizationParams:
         self.lambda_dist_from_iter = 3000
         self.dist_near = 0.2
         self.dist_far = 100.0
+        # opt-in (no reference counterpart): at these iterations the single-GPU training loop scores
+        # every Gaussian by its blend contributions over the training cameras (rain_amd.importance,
+        # `importance_prune_kind` of importance_scores) and removes the lowest-scoring fraction
+        self.importance_prune_iterations = ()
+        self.importance_prune_fraction = 0.0
+        self.importance_prune_kind = "weight_volume"
         for k, v in kw.items():
             setattr(self, k, v)
 
@@ -403,6 +409,20 @@ class GaussianModel:
         self.xyz_gradient_accum = self.xyz_gradient_accum[valid_points_mask]
         self.denom = self.denom[valid_points_mask]
         self.max_radii2D = self.max_radii2D[valid_points_mask]
+
+    def prune_by_importance(self, scores, fraction=None, threshold=None):
+        """Remove the Gaussians rain_amd.importance.prune_mask(scores, fraction, threshold) names (the
+        lowest-scoring `fraction`, ties broken by index so the count is exact, or every score below
+        `threshold`) through prune_points: the Adam moments and the densification statistics follow
+        the kept rows.  Returns the boolean mask of the removed rows."""
+        from .importance import prune_mask
+
+        if scores.shape[0] != self.get_xyz.shape[0]:
+            raise ValueError(f"scores has {scores.shape[0]} entries for {self.get_xyz.shape[0]} Gaussians")
+        mask = prune_mask(scores, fraction=fraction, threshold=threshold).to(self.get_xyz.device)
+        if bool(mask.any()):
+            self.prune_points(mask)
+        return mask
 
     def cat_tensors_to_optimizer(self, tensors_dict):
         optimizable_tensors = {}

@@ -236,6 +236,7 @@ class Trainer:
             raise ValueError("fused step needs a HIP device, the default loss and the default pipeline")
         self._geometry_weight(0)  # a non-zero lambda_normal on the sharded paths is refused here already
         self._distortion_weight(0)  # and so is a non-zero lambda_dist
+        self._importance_prune_now(0)  # and importance pruning
 
     def _low_pass_and_view(self, iteration):
         g, opt, cfg = self.g, self.opt, self.cfg
@@ -328,6 +329,28 @@ class Trainer:
                              "GPU or set lambda_dist = 0")
         return lam if iteration >= int(getattr(self.opt, "lambda_dist_from_iter", 0)) else 0.0
 
+    def _importance_prune_now(self, iteration: int) -> bool:
+        """Whether this iteration ends with an importance prune (OptimizationParams.importance_prune_iterations,
+        with a positive importance_prune_fraction); the defaults never do."""
+        its = tuple(getattr(self.opt, "importance_prune_iterations", ()) or ())
+        if not its:
+            return False
+        if self.sharded:
+            raise ValueError("importance_prune_iterations needs the single-GPU step: the Gaussian-sharded / "
+                             "multi-rank steps have no contribution statistics; train on one GPU or leave it empty")
+        return iteration in its and float(getattr(self.opt, "importance_prune_fraction", 0.0) or 0.0) > 0.0
+
+    def _importance_prune(self):
+        """Score every Gaussian over the training cameras and remove the lowest-scoring fraction.  The
+        parameters are new tensors afterwards, as after a densify: the next step runs a normal forward."""
+        from . import importance
+
+        opt = self.opt
+        with torch.no_grad():
+            stats = importance.accumulate_contributions(self.g, self.cams, self.pipe, self.background)
+            scores = importance.importance_scores(stats, self.g, kind=opt.importance_prune_kind)
+            self.g.prune_by_importance(scores, fraction=float(opt.importance_prune_fraction))
+
     def _dist_range(self):
         return float(getattr(self.opt, "dist_near", 0.2)), float(getattr(self.opt, "dist_far", 100.0))
 
@@ -397,6 +420,7 @@ class Trainer:
 
         lam_n = self._geometry_weight(iteration)  # refuses the sharded steps when the weight is set
         lam_t = self._distortion_weight(iteration)  # likewise
+        prune_now = self._importance_prune_now(iteration)  # likewise
         if self._owner is not None:
             return self._step_owner(iteration, sync_loss)
 
@@ -440,7 +464,7 @@ class Trainer:
         # the next step's frame, preprocessed by this step's backward: only when this step's Adam runs
         # inside that backward (no densify / reset replacing parameters) and the SH degree stays
         next_frame = None
-        if (fuse_adam and self.fuse_next and not self.sharded and iteration + 1 < opt.iterations
+        if (fuse_adam and self.fuse_next and not self.sharded and iteration + 1 < opt.iterations and not prune_now
                 and not self._sh_steps_up(iteration + 1) and not lam_n and not self._geometry_weight(iteration + 1)
                 and not lam_t and not self._distortion_weight(iteration + 1)):
             low_pass_now = self.low_pass
@@ -479,6 +503,8 @@ class Trainer:
             else:
                 fused.backward(st, dimg, grads, stats, adam=adam, next_frame=next_frame)
             densified = self._finish(iteration, flat, densify_now, reset_now, adam_done=fuse_adam)
+        if prune_now:  # after the optimizer step; no next-frame geometry was prepared
+            self._importance_prune()
         if self._pending is not None:  # the parameters the pending geometry was computed from
             self._pending[5] = self._params_signature()
         return StepInfo(loss=float(loss.item()) if sync_loss else None, num_gaussians=g.get_xyz.shape[0],
@@ -546,6 +572,7 @@ class Trainer:
         g, opt = self.g, self.opt
         lam_n = self._geometry_weight(iteration)
         lam_t = self._distortion_weight(iteration)
+        prune_now = self._importance_prune_now(iteration)
         vidx, cam = self._low_pass_and_view(iteration)
         densify_phase = iteration < opt.densify_until_iter
         densify_now, reset_now = self._events(iteration)
@@ -580,5 +607,7 @@ class Trainer:
                 g.update_max_radii(radii, vis)
                 g.add_densification_stats(vsp, vis)
             densified = self._finish(iteration, flat, densify_now, reset_now)
+        if prune_now:
+            self._importance_prune()
         return StepInfo(loss=float(loss.item()) if sync_loss else None, num_gaussians=g.get_xyz.shape[0],
                         view=vidx, low_pass=self.low_pass, densified=densified)
