@@ -153,28 +153,24 @@ def raster():
         L.rr_forward.restype = ci
         L.rr_forward.argtypes = [fp, cp, gp, vp, vp, sz, vp, sz, vp, sz, ctypes.POINTER(ci), ctypes.POINTER(ci),
                                  ctypes.POINTER(sz), vp, vp, vp]
-        L.rr_backward.restype = ci
-        L.rr_backward.argtypes = [fp, cp, gp, vp, vp, vp, vp, ci, vp, vp, sz, ctypes.POINTER(RRGrads), vp]
-        # rr_backward plus dL_ddepth, dL_dalpha after dL_dpix (depth / accumulated-alpha gradients)
-        L.rr_backward_aux.restype = ci
-        L.rr_backward_aux.argtypes = [fp, cp, gp, vp, vp, vp, vp, ci, vp, vp, vp, vp, sz, ctypes.POINTER(RRGrads), vp]
-        # rr_backward_aux plus the camera-gradient block before the stream
+        # the backward ladder: every entry is rr_backward with more maps after dL_dpix (dL_ddepth, dL_dalpha;
+        # then dL_dnormal; then dL_dmoments, dist_near, dist_far), rr_backward_camera is rr_backward_aux with
+        # the camera-gradient block before the stream
+        cf, grp = ctypes.c_float, ctypes.POINTER(RRGrads)
+        head = [fp, cp, gp, vp, vp, vp, vp, ci, vp]  # ..., geom, image, binning, num_rendered, dL_dpix
+        tail = [vp, sz, grp, vp]                     # workspace, workspace_bytes, out, stream
+        aux = head + [vp, vp]
+        for name, argtypes in (("rr_backward", head + tail), ("rr_backward_aux", aux + tail),
+                               ("rr_backward_camera", aux + tail[:-1] + [ctypes.POINTER(RRCameraGrads), vp]),
+                               ("rr_backward_aux_normal", aux + [vp] + tail),
+                               ("rr_backward_aux_dist", aux + [vp, vp, cf, cf] + tail)):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = argtypes
         L.rr_camera_grad_scratch_bytes.restype = sz
         L.rr_camera_grad_scratch_bytes.argtypes = [ci]
-        L.rr_backward_camera.restype = ci
-        L.rr_backward_camera.argtypes = [fp, cp, gp, vp, vp, vp, vp, ci, vp, vp, vp, vp, sz, ctypes.POINTER(RRGrads),
-                                         ctypes.POINTER(RRCameraGrads), vp]
-        L.rr_backward_aux_normal.restype = ci
-        L.rr_backward_aux_normal.argtypes = [fp, cp, gp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, sz,
-                                             ctypes.POINTER(RRGrads), vp]
         # rr_forward_render_aux plus out_moments, dist_near, dist_far before the stream
-        cf = ctypes.c_float
         L.rr_forward_render_dist.restype = ci
         L.rr_forward_render_dist.argtypes = [fp, cp, gp, vp, vp, vp, vp, sz, ci, vp, vp, vp, vp, cf, cf, vp]
-        # rr_backward_aux_normal plus dL_dmoments, dist_near, dist_far after dL_dnormal
-        L.rr_backward_aux_dist.restype = ci
-        L.rr_backward_aux_dist.argtypes = [fp, cp, gp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, cf, cf, vp, sz,
-                                           ctypes.POINTER(RRGrads), vp]
         L.rr_render_alpha.restype = ci
         L.rr_render_alpha.argtypes = [fp, vp, vp, vp]
         # frame, radii, geom, image, binning, num_rendered, pixel_weight, accumulate, out [P] rr_contrib, stream

@@ -537,7 +537,7 @@ int render_tiles(const rr_frame* f, const Geom& gm, const Img& im, const Bin& bn
 // Binning + blend of a frame whose pairs were just counted (count_pairs) into this image buffer.
 int render_frame(const rr_frame* f, const rr_camera* cam, const int* radii, void* geom_buffer, void* image_buffer,
                  void* binning_buffer, size_t binning_bytes, int num_pairs, float* out_color, float* out_depth,
-                 float* out_normal, void* stream, const DistFwdArgs& dm = DistFwdArgs{}) {
+                 float* out_normal, void* stream, const DistFwdArgs& dm) {  // dm.out_moments null: no moment maps
     const int P = f->P, W = f->width, H = f->height, L = num_pairs;
     const int cull = (f->flags & RR_FLAG_NO_TILE_CULLING) ? 0 : 1;
     const WsRange reg = std::exchange(g_hand.fwd_ws, WsRange{});  // used by this render, or dropped by it
@@ -587,20 +587,16 @@ int finish_forward(const rr_frame* f, const rr_camera* cam, const int* radii, vo
     // (rr_forward only: rr_forward_from_geometry refuses the flag before it counts)
     if (f->flags & RR_FLAG_AUX_NORMAL) return fail(RR_ERR_ARG, "RR_FLAG_AUX_NORMAL: use rr_forward_render_aux");
     return render_frame(f, cam, radii, geom_buffer, image_buffer, binning_buffer, binning_bytes, num_pairs, out_color,
-                        out_depth, nullptr, stream);
+                        out_depth, nullptr, stream, DistFwdArgs{});
 }
 
 // Accumulator clear (+ the backward's tile order) and the blend backward: gacc [P][GACC_STRIDE]
-// receives every Gaussian's dmean2D / dconic / dopacity / dcolor sums of the frame.  With dL_ddepth or
-// dL_dalpha (rr_backward_aux) the depth / alpha variant runs and slot 9 receives dL/d(view depth); with
-// dL_dnormal (rr_backward_aux_normal) the normal variant runs and slots 10..12 receive dL/d(normal); with
-// dL_dmoments (rr_backward_aux_dist) the moment variant of either runs (slot 9 also receives the moments'
-// dL/d(view depth)).
+// receives every Gaussian's dmean2D / dconic / dopacity / dcolor sums of the frame.  `mode` is
+// plan_backward(pg, ...).blend (rr_bwd_plan.hpp): the depth modes also leave dL/d(view depth) in slot 9
+// (the moments' share included), the normal modes dL/d(normal) in slots 10..12.
 int blend_backward(const rr_frame* f, const rr_camera* cam, const void* geom_buffer, const void* image_buffer,
-                   const void* binning_buffer, int L, const float* dL_dpix, float* gacc, hipStream_t st,
-                   const float* dL_ddepth = nullptr, const float* dL_dalpha = nullptr,
-                   const float* dL_dnormal = nullptr, const float* dL_dmoments = nullptr, float dist_near = 0.f,
-                   float dist_far = 0.f) {
+                   const void* binning_buffer, int L, const PixelGrads& pg, BlendBwdMode mode, float* gacc,
+                   hipStream_t st) {
     const int P = f->P, W = f->width, H = f->height;
     const Geom gm = carve_geom(const_cast<void*>(geom_buffer), P);
     const Img im = carve_img(const_cast<void*>(image_buffer), W, H);
@@ -629,28 +625,21 @@ int blend_backward(const rr_frame* f, const rr_camera* cam, const void* geom_buf
         b.W = W; b.H = H; b.gx = gx; b.gy = gy;
         b.ranges = im.ranges; b.ranges_b = im.ranges_b; b.point_list = bn.point_list; b.splats = gm.splats;
         b.tile_max = im.tile_max;
-        b.final_T = im.final_T; b.n_contrib = im.n_contrib; b.bg = cam->background; b.dL_dpix = dL_dpix;
+        b.final_T = im.final_T; b.n_contrib = im.n_contrib; b.bg = cam->background; b.dL_dpix = pg.dL_dpix;
         b.gacc = gacc;
         b.order = order;
-        if (dL_dmoments)
-            launch_blend_bwd_dist(b, dL_ddepth, dL_dalpha, dL_dnormal, dL_dnormal ? gm.normals : nullptr, dL_dmoments,
-                                  dist_near, dist_scale_of(dist_near, dist_far), st);
-        else if (dL_dnormal) launch_blend_bwd_normal(b, dL_ddepth, dL_dalpha, dL_dnormal, gm.normals, st);
-        else if (dL_ddepth || dL_dalpha) launch_blend_bwd_aux(b, dL_ddepth, dL_dalpha, st);
-        else launch_blend_bwd(b, st);
+        launch_blend_bwd(b, pg, mode, gm.normals, st);
     }
     RR_STAGE_CHECK("blend backward");
     return RR_OK;
 }
 
-// rr_backward, rr_backward_aux, rr_backward_aux_normal and rr_backward_aux_dist (aux: dL_ddepth, dL_dalpha,
-// dL_dnormal or dL_dmoments given; dL_dpix may then be null)
+// The five rr_backward* entry points: pg holds the output gradients the entry point takes (with an aux
+// map dL_dpix may be null), cg the camera-gradient block of rr_backward_camera or null.
 int backward_impl(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
                   const void* geom_buffer, const void* image_buffer, const void* binning_buffer, int num_rendered,
-                  const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha, const float* dL_dnormal,
-                  void* workspace, size_t workspace_bytes, const rr_grads* out, void* stream,
-                  const float* dL_dmoments = nullptr, float dist_near = 0.f, float dist_far = 0.f,
-                  const rr_camera_grads* cg = nullptr);
+                  const PixelGrads& pg, void* workspace, size_t workspace_bytes, const rr_grads* out,
+                  const rr_camera_grads* cg, void* stream);
 
 }  // namespace
 
@@ -698,7 +687,7 @@ int rr_forward_render_aux(const rr_frame* f, const rr_camera* cam, const rr_gaus
     if (((f->flags & RR_FLAG_AUX_NORMAL) != 0) != (out_normal != nullptr))
         return fail(RR_ERR_ARG, "out_normal must be given exactly when RR_FLAG_AUX_NORMAL is set");
     return render_frame(f, cam, radii, geom_buffer, image_buffer, binning_buffer, binning_bytes, num_pairs, out_color,
-                        out_depth, out_normal, stream);
+                        out_depth, out_normal, stream, DistFwdArgs{});
 }
 
 int rr_forward_render_dist(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
@@ -741,24 +730,24 @@ int rr_forward(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, i
 int rr_backward(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
                 const void* geom_buffer, const void* image_buffer, const void* binning_buffer, int num_rendered,
                 const float* dL_dpix, void* workspace, size_t workspace_bytes, const rr_grads* out, void* stream) {
-    return backward_impl(f, cam, g, radii, geom_buffer, image_buffer, binning_buffer, num_rendered, dL_dpix, nullptr,
-                         nullptr, nullptr, workspace, workspace_bytes, out, stream);
+    return backward_impl(f, cam, g, radii, geom_buffer, image_buffer, binning_buffer, num_rendered,
+                         PixelGrads{dL_dpix}, workspace, workspace_bytes, out, nullptr, stream);
 }
 
 int rr_backward_aux(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
                     const void* geom_buffer, const void* image_buffer, const void* binning_buffer, int num_rendered,
                     const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha, void* workspace,
                     size_t workspace_bytes, const rr_grads* out, void* stream) {
-    return backward_impl(f, cam, g, radii, geom_buffer, image_buffer, binning_buffer, num_rendered, dL_dpix, dL_ddepth,
-                         dL_dalpha, nullptr, workspace, workspace_bytes, out, stream);
+    return backward_impl(f, cam, g, radii, geom_buffer, image_buffer, binning_buffer, num_rendered,
+                         PixelGrads{dL_dpix, dL_ddepth, dL_dalpha}, workspace, workspace_bytes, out, nullptr, stream);
 }
 
 int rr_backward_camera(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
                        const void* geom_buffer, const void* image_buffer, const void* binning_buffer, int num_rendered,
                        const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha, void* workspace,
                        size_t workspace_bytes, const rr_grads* out, const rr_camera_grads* cg, void* stream) {
-    return backward_impl(f, cam, g, radii, geom_buffer, image_buffer, binning_buffer, num_rendered, dL_dpix, dL_ddepth,
-                         dL_dalpha, nullptr, workspace, workspace_bytes, out, stream, nullptr, 0.f, 0.f, cg);
+    return backward_impl(f, cam, g, radii, geom_buffer, image_buffer, binning_buffer, num_rendered,
+                         PixelGrads{dL_dpix, dL_ddepth, dL_dalpha}, workspace, workspace_bytes, out, cg, stream);
 }
 
 int rr_backward_aux_normal(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
@@ -766,8 +755,9 @@ int rr_backward_aux_normal(const rr_frame* f, const rr_camera* cam, const rr_gau
                            int num_rendered, const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha,
                            const float* dL_dnormal, void* workspace, size_t workspace_bytes, const rr_grads* out,
                            void* stream) {
-    return backward_impl(f, cam, g, radii, geom_buffer, image_buffer, binning_buffer, num_rendered, dL_dpix, dL_ddepth,
-                         dL_dalpha, dL_dnormal, workspace, workspace_bytes, out, stream);
+    return backward_impl(f, cam, g, radii, geom_buffer, image_buffer, binning_buffer, num_rendered,
+                         PixelGrads{dL_dpix, dL_ddepth, dL_dalpha, dL_dnormal}, workspace, workspace_bytes, out,
+                         nullptr, stream);
 }
 
 int rr_backward_aux_dist(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
@@ -775,9 +765,9 @@ int rr_backward_aux_dist(const rr_frame* f, const rr_camera* cam, const rr_gauss
                          int num_rendered, const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha,
                          const float* dL_dnormal, const float* dL_dmoments, float dist_near, float dist_far,
                          void* workspace, size_t workspace_bytes, const rr_grads* out, void* stream) {
-    return backward_impl(f, cam, g, radii, geom_buffer, image_buffer, binning_buffer, num_rendered, dL_dpix, dL_ddepth,
-                         dL_dalpha, dL_dnormal, workspace, workspace_bytes, out, stream, dL_dmoments, dist_near,
-                         dist_far);
+    return backward_impl(f, cam, g, radii, geom_buffer, image_buffer, binning_buffer, num_rendered,
+                         PixelGrads{dL_dpix, dL_ddepth, dL_dalpha, dL_dnormal, dL_dmoments, dist_near, dist_far},
+                         workspace, workspace_bytes, out, nullptr, stream);
 }
 
 int rr_render_alpha(const rr_frame* f, const void* image_buffer, float* out_alpha, void* stream) {
@@ -832,12 +822,11 @@ namespace {
 
 int backward_impl(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g, const int* radii,
                   const void* geom_buffer, const void* image_buffer, const void* binning_buffer, int num_rendered,
-                  const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha, const float* dL_dnormal,
-                  void* workspace, size_t workspace_bytes, const rr_grads* out, void* stream, const float* dL_dmoments,
-                  float dist_near, float dist_far, const rr_camera_grads* cg) {
+                  const PixelGrads& pg, void* workspace, size_t workspace_bytes, const rr_grads* out,
+                  const rr_camera_grads* cg, void* stream) {
     int rc = validate(f, cam, g, false);
     if (rc) return rc;
-    if (dL_dmoments && !dist_range_ok(dist_near, dist_far))
+    if (pg.dL_dmoments && !dist_range_ok(pg.dist_near, pg.dist_far))
         return fail(RR_ERR_ARG, "dist_near / dist_far must be 0 < near < far, or both 0 (metric depth)");
     const int P = f->P, W = f->width, H = f->height, L = num_rendered;
     if (cg) {  // camera gradients (rr_backward_camera): every refusal before any device work
@@ -845,7 +834,7 @@ int backward_impl(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g
             return fail(RR_ERR_ARG, "rr_camera_grads: null gradient output");
         if (!cg->scratch || ((uintptr_t)cg->scratch & 15u) != 0)
             return fail(RR_ERR_ARG, "rr_camera_grads: scratch is null or not 16-byte aligned");
-        if (dL_dnormal || dL_dmoments)
+        if (pg.dL_dnormal || pg.dL_dmoments)
             return fail(RR_ERR_ARG, "camera gradients do not combine with dL_dnormal / dL_dmoments yet");
         if (out && (out->adam || out->next))
             return fail(RR_ERR_ARG, "camera gradients do not combine with rr_grads.adam / rr_grads.next");
@@ -861,10 +850,9 @@ int backward_impl(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g
         }
         return RR_OK;
     }
-    const bool aux = dL_ddepth || dL_dalpha || dL_dnormal || dL_dmoments;
-    if (!out || (!dL_dpix && !aux) || !radii || !geom_buffer || !image_buffer || !workspace)
+    if (!out || !pg.any() || !radii || !geom_buffer || !image_buffer || !workspace)
         return fail(RR_ERR_ARG, "null buffer");
-    if (dL_dnormal) {
+    if (pg.dL_dnormal) {
         if (!(f->flags & RR_FLAG_AUX_NORMAL))
             return fail(RR_ERR_ARG, "dL_dnormal needs a frame rendered with RR_FLAG_AUX_NORMAL");
         if (!g->scales || !g->rotations)
@@ -903,8 +891,8 @@ int backward_impl(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g
     }
     hipStream_t st = (hipStream_t)stream;
     float* gacc = static_cast<float*>(workspace);
-    if (int rc2 = blend_backward(f, cam, geom_buffer, image_buffer, binning_buffer, L, dL_dpix, gacc, st, dL_ddepth,
-                                 dL_dalpha, dL_dnormal, dL_dmoments, dist_near, dist_far))
+    const BwdPlan plan = plan_backward(pg, cg != nullptr);
+    if (int rc2 = blend_backward(f, cam, geom_buffer, image_buffer, binning_buffer, L, pg, plan.blend, gacc, st))
         return rc2;
     {
         StageTimer tm(RR_STAGE_GAUSS_BWD, st);
@@ -927,12 +915,10 @@ int backward_impl(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g
             a.next = n;
             a.has_next = 1;
         }
-        if (cg)
+        if (plan.gauss == kGaussBwdCam)
             launch_gauss_bwd_cam(a, static_cast<float*>(cg->scratch), cg->dL_dviewmatrix, cg->dL_dprojmatrix,
                                  cg->dL_dcampos, st);
-        else if (dL_dnormal) launch_gauss_bwd_normal(a, st);
-        else if (aux) launch_gauss_bwd_depth(a, st);
-        else launch_gauss_bwd(a, st);
+        else launch_gauss_bwd(a, plan.gauss, st);
     }
     RR_STAGE_CHECK("gaussian backward");
     return RR_OK;
@@ -1094,7 +1080,7 @@ int rr_forward_render_geometry(const rr_frame* f, const rr_camera* cam, const in
     if (f->P == 0) return RR_OK;
     if (!radii || !cam->background) return fail(RR_ERR_ARG, "null buffer");
     return render_frame(f, cam, radii, geom_buffer, image_buffer, binning_buffer, binning_bytes, num_pairs, out_color,
-                        out_depth, nullptr, stream);
+                        out_depth, nullptr, stream, DistFwdArgs{});
 }
 
 int rr_backward_records(const rr_frame* f, const rr_camera* cam, const int* radii, const void* geom_buffer,
@@ -1112,7 +1098,8 @@ int rr_backward_records(const rr_frame* f, const rr_camera* cam, const int* radi
     if (workspace_bytes < rr_backward_workspace_bytes(P)) return fail(RR_ERR_CAPACITY, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
     float* gacc = static_cast<float*>(workspace);
-    if (int rc = blend_backward(f, cam, geom_buffer, image_buffer, binning_buffer, num_rendered, dL_dpix, gacc, st))
+    if (int rc = blend_backward(f, cam, geom_buffer, image_buffer, binning_buffer, num_rendered, PixelGrads{dL_dpix},
+                                kBlendBwdPlain, gacc, st))
         return rc;
     launch_pack_records(gacc, radii, P, rows_per_rank, rows_per_rank > 0 ? std::min(chunk_rows, rows_per_rank) : 1,
                         records, st);

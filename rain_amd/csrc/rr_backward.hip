@@ -598,14 +598,14 @@ __global__ __launch_bounds__(kGB1) void k_gauss_bwd(GaussBwdArgs a) {
     gauss_bwd_block<DEG, false, kGB1>(a, nullptr, s_sh, s_sh);
 }
 
-// The depth / alpha backward's variant (launch_gauss_bwd_depth): the same kernel reading slot 9.
+// The depth / alpha backward's variant (kGaussBwdDepth): the same kernel reading slot 9.
 template <int DEG>
 __global__ __launch_bounds__(kGB1) void k_gauss_bwd_depth(GaussBwdArgs a) {
     __shared__ float s_sh[kGB1 * kShStride];
     gauss_bwd_block<DEG, false, kGB1, 1>(a, nullptr, s_sh, s_sh);
 }
 
-// The normal backward's variant (launch_gauss_bwd_normal): slots 9 and 10..12.
+// The normal backward's variant (kGaussBwdNormal): slots 9 and 10..12.
 template <int DEG>
 __global__ __launch_bounds__(kGB1) void k_gauss_bwd_normal(GaussBwdArgs a) {
     __shared__ float s_sh[kGB1 * kShStride];
@@ -1044,8 +1044,19 @@ void launch_pack_records(const float* gacc, const int* radii, int P, int Q, int 
     if (P > 0) k_pack_records<<<(P + 255) / 256, 256, 0, st>>>(gacc, radii, P, Q, chunk_rows, rec);
 }
 
-template <int AUX>
-static void launch_gauss_bwd_impl(const GaussBwdArgs& a, hipStream_t st) {
+// The kernel of (mode, SH degree); kGaussBwdCam has its own launcher below.
+using GaussBwdKernel = void (*)(GaussBwdArgs);
+static const GaussBwdKernel kGaussBwdKernels[3][4] = {
+    {k_gauss_bwd<0>, k_gauss_bwd<1>, k_gauss_bwd<2>, k_gauss_bwd<3>},
+    {k_gauss_bwd_depth<0>, k_gauss_bwd_depth<1>, k_gauss_bwd_depth<2>, k_gauss_bwd_depth<3>},
+    {k_gauss_bwd_normal<0>, k_gauss_bwd_normal<1>, k_gauss_bwd_normal<2>, k_gauss_bwd_normal<3>},
+};
+static int sh_degree_of(const GaussBwdArgs& a) {
+    const int d = a.shs ? a.D : 0;
+    return d >= 0 && d < 3 ? d : 3;
+}
+
+void launch_gauss_bwd(const GaussBwdArgs& a, GaussBwdMode mode, hipStream_t st) {
     if (a.P == 0) return;
     if (kGB1 != 256 && a.has_next) {  // the next frame's block sums are accumulated atomically
         const size_t nbs = ((size_t)a.P + 255) / 256;
@@ -1054,35 +1065,8 @@ static void launch_gauss_bwd_impl(const GaussBwdArgs& a, hipStream_t st) {
     }
     // a.M <= 16 is validated by the API: the LDS row holds at most 16 coefficients
     const int nb = (a.P + kGB1 - 1) / kGB1;
-    if constexpr (AUX == 2) {
-        switch (a.shs ? a.D : 0) {
-            case 0: k_gauss_bwd_normal<0><<<nb, kGB1, 0, st>>>(a); break;
-            case 1: k_gauss_bwd_normal<1><<<nb, kGB1, 0, st>>>(a); break;
-            case 2: k_gauss_bwd_normal<2><<<nb, kGB1, 0, st>>>(a); break;
-            default: k_gauss_bwd_normal<3><<<nb, kGB1, 0, st>>>(a); break;
-        }
-        return;
-    }
-    if constexpr (AUX == 1) {
-        switch (a.shs ? a.D : 0) {
-            case 0: k_gauss_bwd_depth<0><<<nb, kGB1, 0, st>>>(a); break;
-            case 1: k_gauss_bwd_depth<1><<<nb, kGB1, 0, st>>>(a); break;
-            case 2: k_gauss_bwd_depth<2><<<nb, kGB1, 0, st>>>(a); break;
-            default: k_gauss_bwd_depth<3><<<nb, kGB1, 0, st>>>(a); break;
-        }
-        return;
-    }
-    switch (a.shs ? a.D : 0) {
-        case 0: k_gauss_bwd<0><<<nb, kGB1, 0, st>>>(a); break;
-        case 1: k_gauss_bwd<1><<<nb, kGB1, 0, st>>>(a); break;
-        case 2: k_gauss_bwd<2><<<nb, kGB1, 0, st>>>(a); break;
-        default: k_gauss_bwd<3><<<nb, kGB1, 0, st>>>(a); break;
-    }
+    kGaussBwdKernels[mode][sh_degree_of(a)]<<<nb, kGB1, 0, st>>>(a);
 }
-
-void launch_gauss_bwd(const GaussBwdArgs& a, hipStream_t st) { launch_gauss_bwd_impl<0>(a, st); }
-void launch_gauss_bwd_depth(const GaussBwdArgs& a, hipStream_t st) { launch_gauss_bwd_impl<1>(a, st); }
-void launch_gauss_bwd_normal(const GaussBwdArgs& a, hipStream_t st) { launch_gauss_bwd_impl<2>(a, st); }
 
 int cam_grad_rows(int P) { return P > 0 ? (P + kGB1 - 1) / kGB1 : 1; }
 
@@ -1091,12 +1075,9 @@ void launch_gauss_bwd_cam(const GaussBwdArgs& a, float* partials, float* d_view,
     const int nb = cam_grad_rows(a.P);
     if (a.P > 0) {
         // a.M <= 16 is validated by the API; no fused step and no next frame here (rr_backward_camera)
-        switch (a.shs ? a.D : 0) {
-            case 0: k_gauss_bwd_cam<0><<<nb, kGB1, 0, st>>>(a, partials); break;
-            case 1: k_gauss_bwd_cam<1><<<nb, kGB1, 0, st>>>(a, partials); break;
-            case 2: k_gauss_bwd_cam<2><<<nb, kGB1, 0, st>>>(a, partials); break;
-            default: k_gauss_bwd_cam<3><<<nb, kGB1, 0, st>>>(a, partials); break;
-        }
+        static void (*const kernels[4])(GaussBwdArgs, float*) = {k_gauss_bwd_cam<0>, k_gauss_bwd_cam<1>,
+                                                                 k_gauss_bwd_cam<2>, k_gauss_bwd_cam<3>};
+        kernels[sh_degree_of(a)]<<<nb, kGB1, 0, st>>>(a, partials);
     }
     k_cam_grad_reduce<<<1, kCamRedGroups * kCamRow, 0, st>>>(partials, a.P > 0 ? nb : 0, d_view, d_proj, d_campos);
 }

@@ -68,13 +68,7 @@ namespace rr {
 // bench scene, the spilling build is again the faster one (blend backward 0.314 / 0.300 vs 0.335 /
 // 0.321 ms), so it is built that way (RR_BWD_NDIST_OCC).  The three older
 // modes ignore the three extra arguments and compile to the code they had before.
-enum BlendBwdMode {
-    kBlendBwdPlain = 0,
-    kBlendBwdDepth = 1,
-    kBlendBwdNormal = 2,
-    kBlendBwdDist = 3,        // depth + moments
-    kBlendBwdNormalDist = 4,  // depth + normal + moments
-};
+// (BlendBwdMode: rr_bwd_plan.hpp)
 #ifndef RR_BWD_NDIST_OCC
 #define RR_BWD_NDIST_OCC 3
 #endif
@@ -439,35 +433,34 @@ void launch_bwd_prologue(float* gacc, size_t nfloats, int T, const uint32_t* til
                                                                     ord ? order : nullptr, order_flag);
 }
 
-void launch_blend_bwd(const BlendBwdArgs& a, hipStream_t st) {
-    const int T = a.gx * a.gy;
-    // a.order: from the prologue or the phase-B duplicate
-    if (T > 0) k_blend_bwd<kBlendBwdPlain><<<T, 64, 0, st>>>(a, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f);
-}
-
-void launch_blend_bwd_aux(const BlendBwdArgs& a, const float* dL_ddepth, const float* dL_dalpha, hipStream_t st) {
-    const int T = a.gx * a.gy;
-    if (T > 0) k_blend_bwd<kBlendBwdDepth><<<T, 64, 0, st>>>(a, dL_ddepth, dL_dalpha, nullptr, nullptr, nullptr, 0.f, 0.f);
-}
-
-void launch_blend_bwd_normal(const BlendBwdArgs& a, const float* dL_ddepth, const float* dL_dalpha,
-                             const float* dL_dnormal, const float4* normals, hipStream_t st) {
-    const int T = a.gx * a.gy;
-    if (T > 0)
-        k_blend_bwd<kBlendBwdNormal><<<T, 64, 0, st>>>(a, dL_ddepth, dL_dalpha, dL_dnormal, normals, nullptr, 0.f, 0.f);
-}
-
-void launch_blend_bwd_dist(const BlendBwdArgs& a, const float* dL_ddepth, const float* dL_dalpha,
-                           const float* dL_dnormal, const float4* normals, const float* dL_dmoments, float near,
-                           float scale, hipStream_t st) {
+// One launch of the blend backward in `mode` (rr_bwd_plan.hpp plan_backward): each mode is handed the
+// maps it reads and null / 0 for the rest.  a.order: from the prologue or the phase-B duplicate.
+void launch_blend_bwd(const BlendBwdArgs& a, const PixelGrads& g, BlendBwdMode mode, const float4* normals,
+                      hipStream_t st) {
     const int T = a.gx * a.gy;
     if (T == 0) return;
-    if (dL_dnormal)
-        k_blend_bwd<kBlendBwdNormalDist><<<T, 64, 0, st>>>(a, dL_ddepth, dL_dalpha, dL_dnormal, normals, dL_dmoments,
-                                                          near, scale);
-    else
-        k_blend_bwd<kBlendBwdDist><<<T, 64, 0, st>>>(a, dL_ddepth, dL_dalpha, nullptr, nullptr, dL_dmoments, near,
-                                                    scale);
+    const float near = g.dist_near, scale = dist_scale_of(g.dist_near, g.dist_far);
+    switch (mode) {
+        case kBlendBwdPlain:
+            k_blend_bwd<kBlendBwdPlain><<<T, 64, 0, st>>>(a, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f);
+            break;
+        case kBlendBwdDepth:
+            k_blend_bwd<kBlendBwdDepth><<<T, 64, 0, st>>>(a, g.dL_ddepth, g.dL_dalpha, nullptr, nullptr, nullptr, 0.f,
+                                                          0.f);
+            break;
+        case kBlendBwdNormal:
+            k_blend_bwd<kBlendBwdNormal><<<T, 64, 0, st>>>(a, g.dL_ddepth, g.dL_dalpha, g.dL_dnormal, normals, nullptr,
+                                                           0.f, 0.f);
+            break;
+        case kBlendBwdDist:
+            k_blend_bwd<kBlendBwdDist><<<T, 64, 0, st>>>(a, g.dL_ddepth, g.dL_dalpha, nullptr, nullptr, g.dL_dmoments,
+                                                         near, scale);
+            break;
+        case kBlendBwdNormalDist:
+            k_blend_bwd<kBlendBwdNormalDist><<<T, 64, 0, st>>>(a, g.dL_ddepth, g.dL_dalpha, g.dL_dnormal, normals,
+                                                               g.dL_dmoments, near, scale);
+            break;
+    }
 }
 
 // Accumulated alpha A = 1 - T_final of the frame last rendered into the image buffer (rr_render_alpha).

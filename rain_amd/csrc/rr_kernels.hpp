@@ -1,5 +1,6 @@
 // rr_kernels.hpp — kernel argument blocks and host launchers shared by the .hip units.
 #pragma once
+#include "rr_bwd_plan.hpp"
 #include "rr_common.hpp"
 #include "../../include/rain_raster.h"
 
@@ -192,12 +193,12 @@ struct GaussBwdArgs {
     PreArgs next;
     int has_next;
 };
-// depth: the accumulators come from the depth / alpha blend backward (launch_blend_bwd_aux) —
-// slot 9, dL/d(view depth), is read and chained into dL/dmeans3D through the view matrix's z row.
-void launch_gauss_bwd_depth(const GaussBwdArgs& a, hipStream_t st);
-// normal: the accumulators come from launch_blend_bwd_normal — slot 9 as above, and slots 10..12,
-// dL/d(view-space unit normal), are chained into dL/drotations (a.scales / a.rotations required).
-void launch_gauss_bwd_normal(const GaussBwdArgs& a, hipStream_t st);
+// The per-Gaussian backward in `mode` (rr_bwd_plan.hpp; not kGaussBwdCam, which is launch_gauss_bwd_cam):
+// kGaussBwdDepth — the accumulators come from an aux blend backward; slot 9, dL/d(view depth), is read
+// and chained into dL/dmeans3D through the view matrix's z row.  kGaussBwdNormal — slot 9 as above, and
+// slots 10..12, dL/d(view-space unit normal), are chained into dL/drotations (a.scales / a.rotations
+// required).
+void launch_gauss_bwd(const GaussBwdArgs& a, GaussBwdMode mode, hipStream_t st);
 // camera (rr_backward_camera): the depth variant plus the gradients of the camera arrays.  Every
 // workgroup leaves the sums of its Gaussians' 27 camera terms in its row of partials
 // ([cam_grad_rows(P)][kCamGradRow] floats, no pre-zeroing), and a one-workgroup pass sums the rows in a
@@ -330,23 +331,17 @@ void launch_dup_gather(const DupArgs<K>& d, hipStream_t st);
 void launch_blend_fwd(const BlendFwdArgs& a, hipStream_t st, const DistFwdArgs* dist = nullptr);
 void launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t st);
 
-void launch_blend_bwd(const BlendBwdArgs& a, hipStream_t st);  // a.order: from launch_bwd_prologue
-// The depth / alpha variant (rr_backward_aux): dL_ddepth / dL_dalpha are [H*W] per-pixel gradients of
-// the depth map and of A = 1 - T_final; either may be null (zero), and so may a.dL_dpix here.  It
-// also accumulates dL/d(view depth) into accumulator slot 9.
-void launch_blend_bwd_aux(const BlendBwdArgs& a, const float* dL_ddepth, const float* dL_dalpha, hipStream_t st);
-// The normal variant (rr_backward_aux_normal): dL_dnormal is the [3,H,W] planar gradient of the aux
-// normal map (any of the four maps may be null), normals the frame's per-Gaussian view-space
-// normals (Geom::normals, written by a forward with RR_FLAG_AUX_NORMAL).  It also accumulates
-// dL/d(normal) into accumulator slots 10..12.
-void launch_blend_bwd_normal(const BlendBwdArgs& a, const float* dL_ddepth, const float* dL_dalpha,
-                             const float* dL_dnormal, const float4* normals, hipStream_t st);
-// The moment variants (rr_backward_aux_dist): dL_dmoments is the [2,H,W] planar gradient of the
-// depth-moment maps (dL/dM1, dL/dM2).  Without dL_dnormal the depth + moments mode runs (normals
-// unused), with it the depth + normal + moments mode.  dL/dm_i times dm/dz is added into slot 9.
-void launch_blend_bwd_dist(const BlendBwdArgs& a, const float* dL_ddepth, const float* dL_dalpha,
-                           const float* dL_dnormal, const float4* normals, const float* dL_dmoments, float near,
-                           float scale, hipStream_t st);
+// The blend backward in `mode` (rr_bwd_plan.hpp plan_backward(g, ...).blend); a.order: from
+// launch_bwd_prologue.  Every map of g may be null (zero), and so may a.dL_dpix outside kBlendBwdPlain.
+//   depth modes (all but plain): g.dL_ddepth / g.dL_dalpha are [H*W] per-pixel gradients of the depth map
+//     and of A = 1 - T_final; dL/d(view depth) is accumulated into accumulator slot 9.
+//   normal modes: g.dL_dnormal is the [3,H,W] planar gradient of the aux normal map, `normals` the frame's
+//     per-Gaussian view-space normals (Geom::normals, written by a forward with RR_FLAG_AUX_NORMAL; unused
+//     by the other modes); dL/d(normal) is accumulated into slots 10..12.
+//   moment modes: g.dL_dmoments is the [2,H,W] planar gradient of the depth-moment maps (dL/dM1, dL/dM2)
+//     under the mapping g.dist_near / g.dist_far; dL/dm_i times dm/dz is added into slot 9.
+void launch_blend_bwd(const BlendBwdArgs& a, const PixelGrads& g, BlendBwdMode mode, const float4* normals,
+                      hipStream_t st);
 void launch_render_alpha(const float* final_T, size_t n, float* out, hipStream_t st);  // out = 1 - final_T
 // clears the nfloats gradient accumulators and, with order, writes the backward's tile order
 // order_flag (may be null): *order_flag == T means the order was already computed this frame
@@ -377,7 +372,6 @@ hipError_t radix_sort_pairs(void* temp, size_t temp_bytes, const K* keys_in, K* 
 // encoded {~start, end} (a key without items keeps {0, 0}; rr_bin.hip k_sortexpand decodes), written by
 // the last pass's scatter
 const char* radix_sort_last_error();  // which check failed in the last radix_sort_pairs call
-void launch_gauss_bwd(const GaussBwdArgs& a, hipStream_t st);
 // The Gaussian-sharded multi-GPU step (rr_gauss_backward_views): one view's camera as the
 // per-Gaussian backward reads it.
 struct ViewCam {

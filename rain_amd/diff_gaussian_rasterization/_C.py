@@ -173,9 +173,9 @@ def _rasterize(background, means3D, colors, opacity, scales, rotations, scale_mo
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier,
                                  cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree,
                                  campos, geomBuffer, R, binningBuffer, imageBuffer, debug, low_pass):
-    return _backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
-                     viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R,
-                     binningBuffer, imageBuffer, debug, low_pass, None, None)
+    return _backward("rasterize_gaussians_backward", background, means3D, radii, colors, scales,
+                     rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy,
+                     dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, low_pass)
 
 
 def rasterize_gaussians_backward_depth(background, means3D, radii, colors, scales, rotations, scale_modifier,
@@ -186,9 +186,10 @@ def rasterize_gaussians_backward_depth(background, means3D, radii, colors, scale
     (dL_dout_depth [1,H,W]) and of the accumulated alpha A = 1 - T_final (dL_dout_alpha [1,H,W])
     added to the colour's (no reference counterpart; rr_backward_aux).  Any of the three output
     gradients may be an empty tensor ("absent": zero), but not all of them.  Same 8-tuple."""
-    return _backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
-                     viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R,
-                     binningBuffer, imageBuffer, debug, low_pass, dL_dout_depth, dL_dout_alpha)
+    return _backward("rasterize_gaussians_backward_depth", background, means3D, radii, colors, scales,
+                     rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy,
+                     dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, low_pass,
+                     dL_dout_depth, dL_dout_alpha)
 
 
 def rasterize_gaussians_backward_camera(background, means3D, radii, colors, scales, rotations, scale_modifier,
@@ -201,9 +202,10 @@ def rasterize_gaussians_backward_camera(background, means3D, radii, colors, scal
     view matrix is reached through the EWA Jacobian, its 3x3 block and the view depth of the depth map;
     the projection through means2D (its z row gets 0); campos through the SH view direction (0 with
     precomputed colours).  The depth and alpha gradients may both be empty (a colour-only loss)."""
-    return _backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
-                     viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R,
-                     binningBuffer, imageBuffer, debug, low_pass, dL_dout_depth, dL_dout_alpha, camera=True)
+    return _backward("rasterize_gaussians_backward_camera", background, means3D, radii, colors, scales,
+                     rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy,
+                     dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, low_pass,
+                     dL_dout_depth, dL_dout_alpha, camera=True)
 
 
 def rasterize_gaussians_backward_normal(background, means3D, radii, colors, scales, rotations, scale_modifier,
@@ -217,9 +219,10 @@ def rasterize_gaussians_backward_normal(background, means3D, radii, colors, scal
     absent this is rasterize_gaussians_backward_depth.  The normal reaches dL_drotations directly and
     every geometric gradient through alpha_i; scales, means3D and the camera get nothing from n_i
     itself (the axis choice and the flip towards the camera are constants).  Same 8-tuple."""
-    return _backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
-                     viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R,
-                     binningBuffer, imageBuffer, debug, low_pass, dL_dout_depth, dL_dout_alpha, dL_dout_normal)
+    return _backward("rasterize_gaussians_backward_normal", background, means3D, radii, colors, scales,
+                     rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy,
+                     dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, low_pass,
+                     dL_dout_depth, dL_dout_alpha, dL_dout_normal)
 
 
 def rasterize_gaussians_backward_dist(background, means3D, radii, colors, scales, rotations, scale_modifier,
@@ -233,31 +236,32 @@ def rasterize_gaussians_backward_dist(background, means3D, radii, colors, scales
     gradients may be an empty tensor ("absent": zero), but not all of them; with dL_dout_moments absent
     this is rasterize_gaussians_backward_normal.  The moments reach dL_dmeans3D through the view depth
     and every geometric gradient through alpha_i.  Same 8-tuple."""
-    return _backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
-                     viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R,
-                     binningBuffer, imageBuffer, debug, low_pass, dL_dout_depth, dL_dout_alpha, dL_dout_normal,
-                     dL_dout_moments, (float(dist_near), float(dist_far)))
+    return _backward("rasterize_gaussians_backward_dist", background, means3D, radii, colors, scales,
+                     rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy,
+                     dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, low_pass,
+                     dL_dout_depth, dL_dout_alpha, dL_dout_normal, dL_dout_moments, (float(dist_near), float(dist_far)))
 
 
 def _present(t):
     return t is not None and t.numel() != 0
 
 
-def _backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
+def _backward(label, background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
               projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
-              imageBuffer, debug, low_pass, dL_dout_depth, dL_dout_alpha, dL_dout_normal=None, dL_dout_moments=None,
-              dist=(0.0, 0.0), camera=False):
+              imageBuffer, debug, low_pass, dL_dout_depth=None, dL_dout_alpha=None, dL_dout_normal=None,
+              dL_dout_moments=None, dist=(0.0, 0.0), camera=False):
+    """Every rasterize_gaussians_backward* above (`label`: its name, for error messages).  An absent map
+    goes to the library as NULL, and the library picks the kernel variants from which maps are there."""
     P = means3D.size(0)
     nrm = _present(dL_dout_normal)
-    mom = _present(dL_dout_moments)
-    aux = _present(dL_dout_depth) or _present(dL_dout_alpha) or nrm or mom
+    maps = (("dL_dout_color", dL_dout_color, NUM_CHANNELS), ("dL_dout_depth", dL_dout_depth, 1),
+            ("dL_dout_alpha", dL_dout_alpha, 1), ("dL_dout_normal", dL_dout_normal, 3),
+            ("dL_dout_moments", dL_dout_moments, 2))
+    aux = any(_present(t) for _, t, _ in maps[1:])
     if aux:  # the frame's size from whichever output gradient is there
-        ref = next(t for t in (dL_dout_color, dL_dout_depth, dL_dout_alpha, dL_dout_normal, dL_dout_moments)
-                   if _present(t))
+        ref = next(t for _, t, _ in maps if _present(t))
         H, W = ref.size(-2), ref.size(-1)
-        for name, t, c in (("dL_dout_color", dL_dout_color, NUM_CHANNELS), ("dL_dout_depth", dL_dout_depth, 1),
-                           ("dL_dout_alpha", dL_dout_alpha, 1), ("dL_dout_normal", dL_dout_normal, 3),
-                           ("dL_dout_moments", dL_dout_moments, 2)):
+        for name, t, c in maps:
             if _present(t) and t.numel() != c * H * W:
                 raise RuntimeError(f"{name} must have {c} x {H} x {W} elements (got {tuple(t.shape)})")
     else:
@@ -275,12 +279,8 @@ def _backward(background, means3D, radii, colors, scales, rotations, scale_modif
         colors=_dev_f32(colors, device, "colors_precomp"), scales=_dev_f32(scales, device, "scales"),
         rotations=_dev_f32(rotations, device, "rotations"), cov3D=_dev_f32(cov3D_precomp, device, "cov3D_precomp"),
         view=_dev_f32(viewmatrix, device, "viewmatrix"), proj=_dev_f32(projmatrix, device, "projmatrix"),
-        sh=_dev_f32(sh, device, "sh"), campos=_dev_f32(campos, device, "campos"),
-        dpix=_dev_f32(dL_dout_color, device, "dL_dout_color"), radii=radii.contiguous(),
-        ddepth=_dev_f32(dL_dout_depth, device, "dL_dout_depth") if aux else None,
-        dalpha=_dev_f32(dL_dout_alpha, device, "dL_dout_alpha") if aux else None,
-        dnormal=_dev_f32(dL_dout_normal, device, "dL_dout_normal") if nrm else None,
-        dmoments=_dev_f32(dL_dout_moments, device, "dL_dout_moments") if mom else None)
+        sh=_dev_f32(sh, device, "sh"), campos=_dev_f32(campos, device, "campos"), radii=radii.contiguous())
+    dpix, ddepth, dalpha, dnormal, dmoments = (_dev_f32(t, device, name) for name, t, _ in maps)
     # opacities are not needed by the backward (the reference does not pass them either)
     frame = _frame(P, degree, M, W, H, tan_fovx, tan_fovy, scale_modifier, low_pass, False, debug)
     if nrm:  # the forward was rasterize_gaussians_aux
@@ -288,55 +288,30 @@ def _backward(background, means3D, radii, colors, scales, rotations, scale_modif
     cam = N.RRCamera(_ptr(keep["bg"]), _ptr(keep["view"]), _ptr(keep["proj"]), _ptr(keep["campos"]))
     gs = N.RRGaussians(_ptr(keep["means3D"]), _ptr(keep["sh"]), _ptr(keep["colors"]), None,
                        _ptr(keep["scales"]), _ptr(keep["rotations"]), _ptr(keep["cov3D"]))
-    out = dict(dL_dmeans2D=torch.empty((P, 3), **fopts), dL_dcolors=torch.empty((P, NUM_CHANNELS), **fopts),
-               dL_dopacity=torch.empty((P, 1), **fopts), dL_dmeans3D=torch.empty((P, 3), **fopts),
-               dL_dcov3D=torch.empty((P, 6), **fopts), dL_dsh=torch.empty((P, M, 3), **fopts),
-               dL_dscales=torch.empty((P, 3), **fopts), dL_drotations=torch.empty((P, 4), **fopts))
-    grads = N.RRGrads(*[_ptr(out[k]) for k in ("dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D",
-                                               "dL_dcov3D", "dL_dsh", "dL_dscales", "dL_drotations")])
+    # dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
+    res = tuple(torch.empty(shape, **fopts)
+                for shape in ((P, 3), (P, NUM_CHANNELS), (P, 1), (P, 3), (P, 6), (P, M, 3), (P, 3), (P, 4)))
+    grads = N.RRGrads(*[_ptr(t) for t in res])
     ws = torch.empty((L.rr_backward_workspace_bytes(P),), dtype=torch.uint8, device=device)
+    head = (ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs), _ptr(keep["radii"]), _ptr(geomBuffer),
+            _ptr(imageBuffer), _ptr(binningBuffer), int(R), _ptr(dpix))
+    tail = (_ptr(ws), ws.numel(), ctypes.byref(grads))
     stream = N.stream_of(means3D)
-    res = (out["dL_dmeans2D"], out["dL_dcolors"], out["dL_dopacity"], out["dL_dmeans3D"], out["dL_dcov3D"],
-           out["dL_dsh"], out["dL_dscales"], out["dL_drotations"])
     if camera:
-        if nrm or mom:
+        if nrm or _present(dL_dout_moments):
             raise RuntimeError("camera gradients do not combine with dL_dout_normal / dL_dout_moments yet")
-        d_view, d_proj, d_campos = torch.empty((4, 4), **fopts), torch.empty((4, 4), **fopts), torch.empty((3,), **fopts)
+        cam_res = (torch.empty((4, 4), **fopts), torch.empty((4, 4), **fopts), torch.empty((3,), **fopts))
         scratch = torch.empty((L.rr_camera_grad_scratch_bytes(P),), dtype=torch.uint8, device=device)
-        cg = N.RRCameraGrads(_ptr(d_view), _ptr(d_proj), _ptr(d_campos), _ptr(scratch), scratch.numel())
-        N.check(L.rr_backward_camera(ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs), _ptr(keep["radii"]),
-                                     _ptr(geomBuffer), _ptr(imageBuffer), _ptr(binningBuffer), int(R),
-                                     _ptr(keep["dpix"]), _ptr(keep["ddepth"]), _ptr(keep["dalpha"]), _ptr(ws),
-                                     ws.numel(), ctypes.byref(grads), ctypes.byref(cg), stream),
-                "rasterize_gaussians_backward_camera")
-        return res + (d_view, d_proj, d_campos)
-    if mom:
-        N.check(L.rr_backward_aux_dist(ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs), _ptr(keep["radii"]),
-                                       _ptr(geomBuffer), _ptr(imageBuffer), _ptr(binningBuffer), int(R),
-                                       _ptr(keep["dpix"]), _ptr(keep["ddepth"]), _ptr(keep["dalpha"]),
-                                       _ptr(keep["dnormal"]), _ptr(keep["dmoments"]), dist[0], dist[1], _ptr(ws),
-                                       ws.numel(), ctypes.byref(grads), stream),
-                "rasterize_gaussians_backward_dist")
-    elif nrm:
-        N.check(L.rr_backward_aux_normal(ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs),
-                                         _ptr(keep["radii"]), _ptr(geomBuffer), _ptr(imageBuffer),
-                                         _ptr(binningBuffer), int(R), _ptr(keep["dpix"]), _ptr(keep["ddepth"]),
-                                         _ptr(keep["dalpha"]), _ptr(keep["dnormal"]), _ptr(ws), ws.numel(),
-                                         ctypes.byref(grads), stream),
-                "rasterize_gaussians_backward_normal")
-    elif aux:
-        N.check(L.rr_backward_aux(ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs), _ptr(keep["radii"]),
-                                  _ptr(geomBuffer), _ptr(imageBuffer), _ptr(binningBuffer), int(R),
-                                  _ptr(keep["dpix"]), _ptr(keep["ddepth"]), _ptr(keep["dalpha"]), _ptr(ws),
-                                  ws.numel(), ctypes.byref(grads), stream),
-                "rasterize_gaussians_backward_depth")
-    else:
-        N.check(L.rr_backward(ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs), _ptr(keep["radii"]),
-                              _ptr(geomBuffer), _ptr(imageBuffer), _ptr(binningBuffer), int(R), _ptr(keep["dpix"]),
-                              _ptr(ws), ws.numel(), ctypes.byref(grads), stream),
-                "rasterize_gaussians_backward")
-    return (out["dL_dmeans2D"], out["dL_dcolors"], out["dL_dopacity"], out["dL_dmeans3D"], out["dL_dcov3D"],
-            out["dL_dsh"], out["dL_dscales"], out["dL_drotations"])
+        cg = N.RRCameraGrads(*[_ptr(t) for t in cam_res], _ptr(scratch), scratch.numel())
+        N.check(L.rr_backward_camera(*head, _ptr(ddepth), _ptr(dalpha), *tail, ctypes.byref(cg), stream), label)
+        return res + cam_res
+    # a colour-only backward stays on rr_backward (the reference's call); every other case is
+    # rr_backward_aux_dist, which with NULL maps is exactly each smaller entry point
+    fn, extra = L.rr_backward, ()
+    if aux:
+        fn, extra = L.rr_backward_aux_dist, (_ptr(ddepth), _ptr(dalpha), _ptr(dnormal), _ptr(dmoments), *dist)
+    N.check(fn(*head, *extra, *tail, stream), label)
+    return res
 
 
 def accumulated_alpha(imageBuffer, H, W):

@@ -101,6 +101,55 @@ class _RasterizeGaussians(torch.autograd.Function):
         return d_means3D, d_means2D, d_sh, d_colors, d_opacities, d_scales, d_rotations, d_cov3D, None
 
 
+def _aux_forward(ctx, inputs, raster_settings, normal=False, dist=None, camera=None):
+    """The forward of the four aux classes: (color, radii, depth, alpha), then the normal map with
+    `normal` (None without it, in a dist frame), then the moment maps with `dist` = (near, far).  `camera` =
+    (viewmatrix, projmatrix, campos) replaces the settings' arrays by these differentiable inputs."""
+    means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp = inputs
+    s = raster_settings
+    if camera is not None:
+        # the kernels read contiguous fp32 arrays; the gradients come back in that layout
+        viewmatrix, projmatrix, campos = (t.detach().to(torch.float32).contiguous() for t in camera)
+        ctx.cam_shapes = (viewmatrix.shape, projmatrix.shape, campos.shape)
+        s = s._replace(viewmatrix=viewmatrix, projmatrix=projmatrix, campos=campos)
+    args = _forward_args(s, means3D, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, sh)
+    fn = _C.rasterize_gaussians_aux if normal else _C.rasterize_gaussians
+    if dist is not None:
+        fn, args = _C.rasterize_gaussians_dist, args + dist + (normal,)
+    num_rendered, color, radii, depth, *maps, geom, binning, img = _invoke(
+        fn, args, s.debug, "snapshot_fw.dump",
+        "\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
+    alpha = _C.accumulated_alpha(img, s.image_height, s.image_width)
+    ctx.raster_settings = s
+    ctx.num_rendered = num_rendered
+    ctx.dist = dist or ()
+    ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning,
+                          img)
+    ctx.mark_non_differentiable(radii)
+    ctx.set_materialize_grads(False)  # an output the loss does not use costs no zero fill and no work
+    return (color, radii, depth, alpha, *maps)
+
+
+def _aux_backward(ctx, fn, grads, n_inputs, camera=False):
+    """The backward of the four aux classes: `grads` = (colour, depth, alpha[, normal[, moments]]) as `fn`,
+    the class's _C entry, takes them after the reference's arguments; one gradient per forward input
+    (`n_inputs`; raster_settings and the plain values get None).  With `camera` the three inputs after
+    raster_settings receive rasterize_gaussians_backward_camera's gradients when one of them needs any."""
+    if all(g is None for g in grads):
+        return (None,) * n_inputs
+    s = ctx.raster_settings
+    grads = _absent_as_empty(*grads)  # "absent" (a NULL pointer in the library)
+    args = _backward_args(s, ctx.saved_tensors, ctx.num_rendered, grads[0]) + grads[1:] + ctx.dist
+    camera = camera and any(ctx.needs_input_grad[9:12])  # a fixed camera: the plain depth backward
+    d_means2D, d_colors, d_opacities, d_means3D, d_cov3D, d_sh, d_scales, d_rotations, *d_cam = _invoke(
+        _C.rasterize_gaussians_backward_camera if camera else fn, args, s.debug, "snapshot_bw.dump",
+        "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
+    # (in the inputs' own shapes: a flat [16] matrix gets a flat gradient)
+    d_cam = tuple(g.view(shape) for g, shape in zip(d_cam, ctx.cam_shapes)) if camera else ()
+    res = (d_means3D, d_means2D, d_sh, d_colors, d_opacities, d_scales, d_rotations, d_cov3D, None) + d_cam
+    return res + (None,) * (n_inputs - len(res))
+
+
 class _RasterizeGaussiansDepth(torch.autograd.Function):
     """_RasterizeGaussians with differentiable depth and accumulated-alpha outputs (no reference
     counterpart; GaussianRasterizer.forward_depth): returns (color, radii, depth, alpha) with
@@ -109,33 +158,12 @@ class _RasterizeGaussiansDepth(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings):
-        s = raster_settings
-        args = _forward_args(s, means3D, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, sh)
-        num_rendered, color, radii, depth, geom, binning, img = _invoke(
-            _C.rasterize_gaussians, args, s.debug, "snapshot_fw.dump",
-            "\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
-        alpha = _C.accumulated_alpha(img, s.image_height, s.image_width)
-        ctx.raster_settings = s
-        ctx.num_rendered = num_rendered
-        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning,
-                              img)
-        ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)  # an output the loss does not use costs no zero fill and no work
-        return color, radii, depth, alpha
+        return _aux_forward(ctx, (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp),
+                            raster_settings)
 
     @staticmethod
     def backward(ctx, grad_out_color, grad_radii, grad_depth, grad_alpha):
-        if grad_out_color is None and grad_depth is None and grad_alpha is None:
-            return (None,) * 9
-        s = ctx.raster_settings
-        empty = torch.Tensor([])  # "absent" (a NULL pointer in the library)
-        grad_out_color, grad_depth, grad_alpha = (empty if g is None else g
-                                                  for g in (grad_out_color, grad_depth, grad_alpha))
-        args = _backward_args(s, ctx.saved_tensors, ctx.num_rendered, grad_out_color) + (grad_depth, grad_alpha)
-        d_means2D, d_colors, d_opacities, d_means3D, d_cov3D, d_sh, d_scales, d_rotations = _invoke(
-            _C.rasterize_gaussians_backward_depth, args, s.debug, "snapshot_bw.dump",
-            "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
-        return d_means3D, d_means2D, d_sh, d_colors, d_opacities, d_scales, d_rotations, d_cov3D, None
+        return _aux_backward(ctx, _C.rasterize_gaussians_backward_depth, (grad_out_color, grad_depth, grad_alpha), 9)
 
 
 class _RasterizeGaussiansCamera(torch.autograd.Function):
@@ -147,46 +175,13 @@ class _RasterizeGaussiansCamera(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings, viewmatrix, projmatrix, campos):
-        # the kernels read contiguous fp32 arrays; the gradients come back in that layout
-        viewmatrix, projmatrix, campos = (t.detach().to(torch.float32).contiguous()
-                                          for t in (viewmatrix, projmatrix, campos))
-        ctx.cam_shapes = (viewmatrix.shape, projmatrix.shape, campos.shape)
-        s = raster_settings._replace(viewmatrix=viewmatrix, projmatrix=projmatrix, campos=campos)
-        args = _forward_args(s, means3D, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, sh)
-        num_rendered, color, radii, depth, geom, binning, img = _invoke(
-            _C.rasterize_gaussians, args, s.debug, "snapshot_fw.dump",
-            "\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
-        alpha = _C.accumulated_alpha(img, s.image_height, s.image_width)
-        ctx.raster_settings = s
-        ctx.num_rendered = num_rendered
-        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning,
-                              img)
-        ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)
-        return color, radii, depth, alpha
+        return _aux_forward(ctx, (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp),
+                            raster_settings, camera=(viewmatrix, projmatrix, campos))
 
     @staticmethod
     def backward(ctx, grad_out_color, grad_radii, grad_depth, grad_alpha):
-        if grad_out_color is None and grad_depth is None and grad_alpha is None:
-            return (None,) * 12
-        s = ctx.raster_settings
-        empty = torch.Tensor([])  # "absent" (a NULL pointer in the library)
-        grad_out_color, grad_depth, grad_alpha = (empty if g is None else g
-                                                  for g in (grad_out_color, grad_depth, grad_alpha))
-        args = _backward_args(s, ctx.saved_tensors, ctx.num_rendered, grad_out_color) + (grad_depth, grad_alpha)
-        if not any(ctx.needs_input_grad[9:12]):  # a fixed camera: the plain depth backward
-            d_means2D, d_colors, d_opacities, d_means3D, d_cov3D, d_sh, d_scales, d_rotations = _invoke(
-                _C.rasterize_gaussians_backward_depth, args, s.debug, "snapshot_bw.dump",
-                "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
-            d_view = d_proj = d_campos = None
-        else:
-            (d_means2D, d_colors, d_opacities, d_means3D, d_cov3D, d_sh, d_scales, d_rotations, d_view, d_proj,
-             d_campos) = _invoke(_C.rasterize_gaussians_backward_camera, args, s.debug, "snapshot_bw.dump",
-                                 "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
-            # (in the inputs' own shapes: a flat [16] matrix gets a flat gradient)
-            d_view, d_proj, d_campos = (g.view(sh) for g, sh in zip((d_view, d_proj, d_campos), ctx.cam_shapes))
-        return (d_means3D, d_means2D, d_sh, d_colors, d_opacities, d_scales, d_rotations, d_cov3D, None, d_view,
-                d_proj, d_campos)
+        return _aux_backward(ctx, _C.rasterize_gaussians_backward_depth, (grad_out_color, grad_depth, grad_alpha), 12,
+                             camera=True)
 
 
 class _RasterizeGaussiansNormal(torch.autograd.Function):
@@ -197,34 +192,13 @@ class _RasterizeGaussiansNormal(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings):
-        s = raster_settings
-        args = _forward_args(s, means3D, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, sh)
-        num_rendered, color, radii, depth, normal, geom, binning, img = _invoke(
-            _C.rasterize_gaussians_aux, args, s.debug, "snapshot_fw.dump",
-            "\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
-        alpha = _C.accumulated_alpha(img, s.image_height, s.image_width)
-        ctx.raster_settings = s
-        ctx.num_rendered = num_rendered
-        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning,
-                              img)
-        ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)
-        return color, radii, depth, alpha, normal
+        return _aux_forward(ctx, (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp),
+                            raster_settings, normal=True)
 
     @staticmethod
     def backward(ctx, grad_out_color, grad_radii, grad_depth, grad_alpha, grad_normal):
-        if grad_out_color is None and grad_depth is None and grad_alpha is None and grad_normal is None:
-            return (None,) * 9
-        s = ctx.raster_settings
-        empty = torch.Tensor([])  # "absent" (a NULL pointer in the library)
-        grad_out_color, grad_depth, grad_alpha, grad_normal = (
-            empty if g is None else g for g in (grad_out_color, grad_depth, grad_alpha, grad_normal))
-        args = _backward_args(s, ctx.saved_tensors, ctx.num_rendered, grad_out_color) + (grad_depth, grad_alpha,
-                                                                                        grad_normal)
-        d_means2D, d_colors, d_opacities, d_means3D, d_cov3D, d_sh, d_scales, d_rotations = _invoke(
-            _C.rasterize_gaussians_backward_normal, args, s.debug, "snapshot_bw.dump",
-            "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
-        return d_means3D, d_means2D, d_sh, d_colors, d_opacities, d_scales, d_rotations, d_cov3D, None
+        return _aux_backward(ctx, _C.rasterize_gaussians_backward_normal,
+                             (grad_out_color, grad_depth, grad_alpha, grad_normal), 9)
 
 
 class _RasterizeGaussiansDist(torch.autograd.Function):
@@ -235,37 +209,13 @@ class _RasterizeGaussiansDist(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings, dist_near, dist_far, normal):
-        s = raster_settings
-        args = _forward_args(s, means3D, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, sh) + \
-            (float(dist_near), float(dist_far), bool(normal))
-        num_rendered, color, radii, depth, nmap, moments, geom, binning, img = _invoke(
-            _C.rasterize_gaussians_dist, args, s.debug, "snapshot_fw.dump",
-            "\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
-        alpha = _C.accumulated_alpha(img, s.image_height, s.image_width)
-        ctx.raster_settings = s
-        ctx.num_rendered = num_rendered
-        ctx.dist = (float(dist_near), float(dist_far))
-        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning,
-                              img)
-        ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)
-        return color, radii, depth, alpha, nmap, moments
+        return _aux_forward(ctx, (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp),
+                            raster_settings, normal=bool(normal), dist=(float(dist_near), float(dist_far)))
 
     @staticmethod
     def backward(ctx, grad_out_color, grad_radii, grad_depth, grad_alpha, grad_normal, grad_moments):
-        gs = (grad_out_color, grad_depth, grad_alpha, grad_normal, grad_moments)
-        if all(g is None for g in gs):
-            return (None,) * 12
-        s = ctx.raster_settings
-        empty = torch.Tensor([])  # "absent" (a NULL pointer in the library)
-        grad_out_color, grad_depth, grad_alpha, grad_normal, grad_moments = (empty if g is None else g for g in gs)
-        args = _backward_args(s, ctx.saved_tensors, ctx.num_rendered, grad_out_color) + (
-            grad_depth, grad_alpha, grad_normal, grad_moments) + ctx.dist
-        d_means2D, d_colors, d_opacities, d_means3D, d_cov3D, d_sh, d_scales, d_rotations = _invoke(
-            _C.rasterize_gaussians_backward_dist, args, s.debug, "snapshot_bw.dump",
-            "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
-        return (d_means3D, d_means2D, d_sh, d_colors, d_opacities, d_scales, d_rotations, d_cov3D, None, None, None,
-                None)
+        return _aux_backward(ctx, _C.rasterize_gaussians_backward_dist,
+                             (grad_out_color, grad_depth, grad_alpha, grad_normal, grad_moments), 12)
 
 
 def _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp):
@@ -289,6 +239,15 @@ def _absent_as_empty(*tensors):
     return tuple(torch.Tensor([]) if t is None else t for t in tensors)
 
 
+def _checked_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp, normal=False):
+    """The preamble of every GaussianRasterizer.forward*: the reference's checks (and, for a frame with the
+    aux normal map, the scale/rotation pair), then the five optional inputs with None as 'absent'."""
+    _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp)
+    if normal and cov3D_precomp is not None:
+        raise Exception(_MSG_NORMAL)
+    return _absent_as_empty(shs, colors_precomp, scales, rotations, cov3D_precomp)
+
+
 class GaussianRasterizer(nn.Module):
     def __init__(self, raster_settings):
         super().__init__()
@@ -301,9 +260,8 @@ class GaussianRasterizer(nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None):
-        _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp)
-        shs, colors_precomp, scales, rotations, cov3D_precomp = _absent_as_empty(shs, colors_precomp, scales,
-                                                                                 rotations, cov3D_precomp)
+        shs, colors_precomp, scales, rotations, cov3D_precomp = _checked_inputs(shs, colors_precomp, scales,
+                                                                                rotations, cov3D_precomp)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                    cov3D_precomp, self.raster_settings)
 
@@ -314,9 +272,8 @@ class GaussianRasterizer(nn.Module):
         sum alpha_i T_i z_i (no background term, not normalised), alpha is 1 - T_final =
         sum alpha_i T_i; expected depth is depth / alpha.  Gradient conventions are the colour
         path's (no mask for the 0.99 alpha clamp, dL/dmeans2D in NDC units)."""
-        _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp)
-        shs, colors_precomp, scales, rotations, cov3D_precomp = _absent_as_empty(shs, colors_precomp, scales,
-                                                                                 rotations, cov3D_precomp)
+        shs, colors_precomp, scales, rotations, cov3D_precomp = _checked_inputs(shs, colors_precomp, scales,
+                                                                                rotations, cov3D_precomp)
         return _RasterizeGaussiansDepth.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                               cov3D_precomp, self.raster_settings)
 
@@ -329,9 +286,8 @@ class GaussianRasterizer(nn.Module):
         reached through the EWA Jacobian, its 3x3 block and the view depth of the depth map; the
         projection through means2D only (its z row gets 0); campos through the SH view direction (0
         with colors_precomp).  Culling, radii and the depth order are discrete and contribute nothing."""
-        _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp)
-        shs, colors_precomp, scales, rotations, cov3D_precomp = _absent_as_empty(shs, colors_precomp, scales,
-                                                                                 rotations, cov3D_precomp)
+        shs, colors_precomp, scales, rotations, cov3D_precomp = _checked_inputs(shs, colors_precomp, scales,
+                                                                                rotations, cov3D_precomp)
         s = self.raster_settings
         return _RasterizeGaussiansCamera.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                                cov3D_precomp, s, s.viewmatrix, s.projmatrix, s.campos)
@@ -344,11 +300,8 @@ class GaussianRasterizer(nn.Module):
         camera; no background term).  Its gradient reaches the rotations directly (the axis choice
         and the flip are constants) and opacity, position and covariance through alpha_i.  Needs the
         scale/rotation pair (cov3D_precomp is refused)."""
-        _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp)
-        if cov3D_precomp is not None:
-            raise Exception(_MSG_NORMAL)
-        shs, colors_precomp, scales, rotations, cov3D_precomp = _absent_as_empty(shs, colors_precomp, scales,
-                                                                                 rotations, cov3D_precomp)
+        shs, colors_precomp, scales, rotations, cov3D_precomp = _checked_inputs(
+            shs, colors_precomp, scales, rotations, cov3D_precomp, normal=True)
         return _RasterizeGaussiansNormal.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                                cov3D_precomp, self.raster_settings)
 
@@ -361,14 +314,11 @@ class GaussianRasterizer(nn.Module):
         itself for dist_near = dist_far = 0.  The per-pixel distortion sum_{i>j} w_i w_j (m_i - m_j)^2 is
         alpha * M2 - M1^2 (rain_amd.loss.fused_distortion_loss).  With `normal` the aux normal map of
         forward_normal() is rendered and differentiated too (needs the scale/rotation pair)."""
-        _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp)
-        if normal and cov3D_precomp is not None:
-            raise Exception(_MSG_NORMAL)
+        shs, colors_precomp, scales, rotations, cov3D_precomp = _checked_inputs(
+            shs, colors_precomp, scales, rotations, cov3D_precomp, normal=normal)
         near, far = float(dist_near), float(dist_far)
         if not ((near == 0.0 and far == 0.0) or (0.0 < near < far < float("inf"))):
             raise Exception(_MSG_DIST)
-        shs, colors_precomp, scales, rotations, cov3D_precomp = _absent_as_empty(shs, colors_precomp, scales,
-                                                                                 rotations, cov3D_precomp)
         return _RasterizeGaussiansDist.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                              cov3D_precomp, self.raster_settings, near, far, bool(normal))
 
@@ -380,9 +330,8 @@ class GaussianRasterizer(nn.Module):
         stats = (sum_w, sum_gw, max_w, count) of _C.gaussian_contributions: over the pixels p Gaussian i
         was blended into, sum_p w_i, sum_p g(p) w_i with g = pixel_weight [H,W] (1 when None), max_p w_i
         and the pixel count, w_i = alpha_i T_i.  `out` [P,4] accumulates views into one buffer."""
-        _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp)
-        shs, colors_precomp, scales, rotations, cov3D = _absent_as_empty(shs, colors_precomp, scales, rotations,
-                                                                         cov3D_precomp)
+        shs, colors_precomp, scales, rotations, cov3D = _checked_inputs(shs, colors_precomp, scales, rotations,
+                                                                        cov3D_precomp)
         s = self.raster_settings
         args = _forward_args(s, means3D, colors_precomp, opacities, scales, rotations, cov3D, shs)
         num_rendered, color, radii, _depth, geom, binning, img = _C.rasterize_gaussians(*args)

@@ -346,38 +346,24 @@ def backward(st: RawFrame, dL_dpix: torch.Tensor, grads: dict | None, stats: tup
         frame.flags |= N.RR_FLAG_WORKSPACE_REGISTERED
     else:
         ws = torch.empty((L.rr_backward_workspace_bytes(st.P),), dtype=torch.uint8, device=dev)
+    head = (ctypes.byref(frame), ctypes.byref(st.cam), ctypes.byref(st.gs), _p(st.radii), _p(st.geom), _p(st.img),
+            _p(st.binning), st.num_rendered, _p(dpix) if dL_dpix is not None else None)
+    tail = (_p(ws), ws.numel(), ctypes.byref(out))
+    stream = N.stream_of(dpix)
     if cam_grads is not None:
         scratch = torch.empty((L.rr_camera_grad_scratch_bytes(st.P),), dtype=torch.uint8, device=dev)
         cg = N.RRCameraGrads(_p(cam_grads[0]), _p(cam_grads[1]), _p(cam_grads[2]), _p(scratch), scratch.numel())
-        N.check(L.rr_backward_camera(ctypes.byref(frame), ctypes.byref(st.cam), ctypes.byref(st.gs), _p(st.radii),
-                                     _p(st.geom), _p(st.img), _p(st.binning), st.num_rendered,
-                                     _p(dpix) if dL_dpix is not None else None, _p(maps[0]), _p(maps[1]), _p(ws),
-                                     ws.numel(), ctypes.byref(out), ctypes.byref(cg), N.stream_of(dpix)),
+        N.check(L.rr_backward_camera(*head, _p(maps[0]), _p(maps[1]), *tail, ctypes.byref(cg), stream),
                 "fused backward (camera)")
         return
-    if maps[3] is not None:
-        N.check(L.rr_backward_aux_dist(ctypes.byref(frame), ctypes.byref(st.cam), ctypes.byref(st.gs), _p(st.radii),
-                                       _p(st.geom), _p(st.img), _p(st.binning), st.num_rendered,
-                                       _p(dpix) if dL_dpix is not None else None, _p(maps[0]), _p(maps[1]),
-                                       _p(maps[2]), _p(maps[3]), st.dist[0], st.dist[1], _p(ws), ws.numel(),
-                                       ctypes.byref(out), N.stream_of(dpix)), "fused backward (distortion)")
-        return
-    if maps[2] is not None:
-        N.check(L.rr_backward_aux_normal(ctypes.byref(frame), ctypes.byref(st.cam), ctypes.byref(st.gs),
-                                         _p(st.radii), _p(st.geom), _p(st.img), _p(st.binning), st.num_rendered,
-                                         _p(dpix) if dL_dpix is not None else None, _p(maps[0]), _p(maps[1]),
-                                         _p(maps[2]), _p(ws), ws.numel(), ctypes.byref(out), N.stream_of(dpix)),
-                "fused backward (normal)")
-        return
+    # a colour-only backward stays on rr_backward; every other case is rr_backward_aux_dist, which with NULL
+    # maps is exactly each smaller entry point: the library picks the kernel variants from the maps given
+    fn, extra, what = L.rr_backward, (), ""
     if aux:
-        N.check(L.rr_backward_aux(ctypes.byref(frame), ctypes.byref(st.cam), ctypes.byref(st.gs), _p(st.radii),
-                                  _p(st.geom), _p(st.img), _p(st.binning), st.num_rendered,
-                                  _p(dpix) if dL_dpix is not None else None, _p(maps[0]), _p(maps[1]), _p(ws),
-                                  ws.numel(), ctypes.byref(out), N.stream_of(dpix)), "fused backward (depth)")
-        return
-    N.check(L.rr_backward(ctypes.byref(frame), ctypes.byref(st.cam), ctypes.byref(st.gs), _p(st.radii),
-                          _p(st.geom), _p(st.img), _p(st.binning), st.num_rendered, _p(dpix), _p(ws), ws.numel(),
-                          ctypes.byref(out), N.stream_of(dpix)), "fused backward")
+        near, far = st.dist if maps[3] is not None else (0.0, 0.0)
+        fn, extra = L.rr_backward_aux_dist, (*[_p(m) for m in maps], near, far)
+        what = " (distortion)" if maps[3] is not None else " (normal)" if maps[2] is not None else " (depth)"
+    N.check(fn(*head, *extra, *tail, stream), "fused backward" + what)
 
 
 def accumulated_alpha(st: RawFrame) -> torch.Tensor:
@@ -386,6 +372,75 @@ def accumulated_alpha(st: RawFrame) -> torch.Tensor:
     if st.P == 0:
         return torch.zeros((1, H, W), dtype=torch.float32, device=st.radii.device)
     return _C.accumulated_alpha(st.img, H, W)
+
+
+_RAW_INPUTS = 18  # forward inputs of the raw-parameter classes (RasterizeRawParamsDist: three more)
+
+
+def _raw_forward(ctx, inputs, aux=True, normal=False, dist=None, camera=False):
+    """The forward of the five classes below on their 18 common `inputs`: (color, radii, depth), with `aux`
+    the accumulated alpha as well (depth then carries gradients), then the aux normal map with `normal`
+    (None without it, in a dist frame), then the moment maps with `dist` = (near, far).  `camera`: the three
+    camera arrays are differentiable inputs."""
+    (xyz, f_dc, f_rest, opacity, scaling, rotation, _means2D, sh_degree, W, H, tanfovx, tanfovy, viewmatrix,
+     projmatrix, campos, bg, low_pass, scale_modifier) = inputs
+    if camera:
+        viewmatrix, projmatrix, campos = (t.detach().to(torch.float32).contiguous()
+                                          for t in (viewmatrix, projmatrix, campos))
+        ctx.cam_shapes = (viewmatrix.shape, projmatrix.shape, campos.shape)
+    color, radii, depth, st = forward_params((xyz, f_dc, f_rest, opacity, scaling, rotation), sh_degree, W, H,
+                                             tanfovx, tanfovy, viewmatrix, projmatrix, campos, bg, low_pass,
+                                             scale_modifier, normal=normal, dist=dist)
+    # the parameters as saved tensors (the reference saves its inputs, __init__.py:85-87): autograd's
+    # version check then rejects a backward after they were modified in place.  The scratch
+    # buffers and camera tensors are saved too, so that autograd frees them after a backward
+    # that does not retain the graph; ctx keeps only the descriptors (plain structs).
+    keep, _p6 = st.keep
+    ctx.save_for_backward(xyz, f_dc, f_rest, opacity, scaling, rotation, st.radii, st.geom, st.img, st.binning,
+                          st.ws, *keep)
+    ctx.desc = (st.frame, st.cam, st.gs, st.num_rendered, st.P, st.M, st.dist)
+    ctx.set_materialize_grads(False)  # an output the loss does not use gets no zero-filled gradient
+    if not aux:
+        ctx.mark_non_differentiable(radii, depth)
+        return color, radii, depth
+    ctx.mark_non_differentiable(radii)
+    maps = (st.normal, st.moments) if dist is not None else (st.normal,) if normal else ()
+    return (color, radii, depth, accumulated_alpha(st), *maps)
+
+
+def _raw_backward(ctx, n_inputs, grad_color, grad_depth=None, grad_alpha=None, grad_normal=None, grad_moments=None,
+                  aux=True, camera=False):
+    """The backward of the five classes below: one gradient per forward input (`n_inputs`), None for the
+    plain values.  An output the loss does not use arrives as None and goes to the library as an absent
+    map; without `aux` (RasterizeRawParams) a missing colour gradient is zeros instead.  With `camera` the
+    three camera inputs get rr_backward_camera's gradients when one of them needs any."""
+    if aux and all(g is None for g in (grad_color, grad_depth, grad_alpha, grad_normal, grad_moments)):
+        return (None,) * n_inputs
+    # (raises if a parameter changed in place since the forward)
+    xyz, f_dc, f_rest, opacity, scaling, rotation, radii, geom, img, binning, ws, *keep = ctx.saved_tensors
+    frame, cam, gs, num_rendered, P, M, dist = ctx.desc
+    p = (xyz, f_dc, opacity, scaling, rotation, f_rest)  # kernel order
+    # the zero-filled workspace serves the first backward only (a retained graph's second one
+    # allocates and clears its own)
+    ws_first = ws if not getattr(ctx, "ws_used", False) else None
+    ctx.ws_used = True
+    st = RawFrame(frame, cam, gs, (tuple(keep), p), radii, geom, img, binning, num_rendered, P, M, ws_first,
+                  dist=dist)
+    fo = dict(dtype=torch.float32, device=xyz.device)
+    if not aux and grad_color is None:  # the image unused by the loss (materialize_grads off)
+        grad_color = torch.zeros((3, frame.height, frame.width), **fo)
+    grads = dict(xyz=torch.empty_like(p[0]), f_dc=torch.empty_like(p[1]), opacity=torch.empty_like(p[2]),
+                 scaling=torch.empty_like(p[3]), rotation=torch.empty_like(p[4]), f_rest=torch.empty_like(p[5]))
+    d2 = torch.empty((P, 3), **fo)
+    cg = None
+    if camera and any(ctx.needs_input_grad[12:15]):  # else a fixed camera: the plain depth backward
+        cg = (torch.empty((4, 4), **fo), torch.empty((4, 4), **fo), torch.empty((3,), **fo))
+    backward(st, grad_color, grads, dmeans2D=d2, dL_ddepth=grad_depth, dL_dalpha=grad_alpha, dL_dnormal=grad_normal,
+             dL_dmoments=grad_moments, cam_grads=cg)
+    # (in the inputs' own shapes: a flat [16] matrix gets a flat gradient)
+    d_cam = tuple(g.view(s) for g, s in zip(cg, ctx.cam_shapes)) if cg is not None else (None,) * 3
+    return (grads["xyz"], grads["f_dc"], grads["f_rest"], grads["opacity"], grads["scaling"], grads["rotation"], d2,
+            None, None, None, None, None, *d_cam) + (None,) * (n_inputs - 15)
 
 
 class RasterizeRawParams(torch.autograd.Function):
@@ -400,40 +455,12 @@ class RasterizeRawParams(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, f_dc, f_rest, opacity, scaling, rotation, means2D, sh_degree, W, H, tanfovx, tanfovy,
                 viewmatrix, projmatrix, campos, bg, low_pass, scale_modifier):
-        color, radii, depth, st = forward_params((xyz, f_dc, f_rest, opacity, scaling, rotation), sh_degree, W, H,
-                                                 tanfovx, tanfovy, viewmatrix, projmatrix, campos, bg, low_pass,
-                                                 scale_modifier)
-        # the parameters as saved tensors (the reference saves its inputs, __init__.py:85-87): autograd's
-        # version check then rejects a backward after they were modified in place.  The scratch
-        # buffers and camera tensors are saved too, so that autograd frees them after a backward
-        # that does not retain the graph; ctx keeps only the descriptors (plain structs).
-        keep, _p6 = st.keep
-        ctx.save_for_backward(xyz, f_dc, f_rest, opacity, scaling, rotation, st.radii, st.geom, st.img, st.binning,
-                              st.ws, *keep)
-        ctx.desc = (st.frame, st.cam, st.gs, st.num_rendered, st.P, st.M)
-        ctx.mark_non_differentiable(radii, depth)
-        ctx.set_materialize_grads(False)  # no zero-filled gradients for radii / depth (two fills)
-        return color, radii, depth
+        return _raw_forward(ctx, (xyz, f_dc, f_rest, opacity, scaling, rotation, means2D, sh_degree, W, H, tanfovx,
+                                  tanfovy, viewmatrix, projmatrix, campos, bg, low_pass, scale_modifier), aux=False)
 
     @staticmethod
     def backward(ctx, grad_color, _grad_radii, _grad_depth):
-        # (raises if a parameter changed in place since the forward)
-        xyz, f_dc, f_rest, opacity, scaling, rotation, radii, geom, img, binning, ws, *keep = ctx.saved_tensors
-        frame, cam, gs, num_rendered, P, M = ctx.desc
-        p = (xyz, f_dc, opacity, scaling, rotation, f_rest)  # kernel order
-        # the zero-filled workspace serves the first backward only (a retained graph's second one
-        # allocates and clears its own)
-        ws_first = ws if not getattr(ctx, "ws_used", False) else None
-        ctx.ws_used = True
-        st = RawFrame(frame, cam, gs, (tuple(keep), p), radii, geom, img, binning, num_rendered, P, M, ws_first)
-        if grad_color is None:  # the image unused by the loss (materialize_grads off)
-            grad_color = torch.zeros((3, frame.height, frame.width), dtype=torch.float32, device=xyz.device)
-        grads = dict(xyz=torch.empty_like(p[0]), f_dc=torch.empty_like(p[1]), opacity=torch.empty_like(p[2]),
-                     scaling=torch.empty_like(p[3]), rotation=torch.empty_like(p[4]), f_rest=torch.empty_like(p[5]))
-        d2 = torch.empty((st.P, 3), dtype=torch.float32, device=p[0].device)
-        backward(st, grad_color, grads, dmeans2D=d2)
-        return (grads["xyz"], grads["f_dc"], grads["f_rest"], grads["opacity"], grads["scaling"], grads["rotation"], d2,
-                None, None, None, None, None, None, None, None, None, None, None)
+        return _raw_backward(ctx, _RAW_INPUTS, grad_color, aux=False)
 
 
 class RasterizeRawParamsDepth(torch.autograd.Function):
@@ -445,36 +472,12 @@ class RasterizeRawParamsDepth(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, f_dc, f_rest, opacity, scaling, rotation, means2D, sh_degree, W, H, tanfovx, tanfovy,
                 viewmatrix, projmatrix, campos, bg, low_pass, scale_modifier):
-        color, radii, depth, st = forward_params((xyz, f_dc, f_rest, opacity, scaling, rotation), sh_degree, W, H,
-                                                 tanfovx, tanfovy, viewmatrix, projmatrix, campos, bg, low_pass,
-                                                 scale_modifier)
-        alpha = accumulated_alpha(st)
-        keep, _p6 = st.keep
-        ctx.save_for_backward(xyz, f_dc, f_rest, opacity, scaling, rotation, st.radii, st.geom, st.img, st.binning,
-                              st.ws, *keep)
-        ctx.desc = (st.frame, st.cam, st.gs, st.num_rendered, st.P, st.M)
-        ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)
-        return color, radii, depth, alpha
+        return _raw_forward(ctx, (xyz, f_dc, f_rest, opacity, scaling, rotation, means2D, sh_degree, W, H, tanfovx,
+                                  tanfovy, viewmatrix, projmatrix, campos, bg, low_pass, scale_modifier))
 
     @staticmethod
     def backward(ctx, grad_color, _grad_radii, grad_depth, grad_alpha):
-        if grad_color is None and grad_depth is None and grad_alpha is None:
-            return (None,) * 18
-        xyz, f_dc, f_rest, opacity, scaling, rotation, radii, geom, img, binning, ws, *keep = ctx.saved_tensors
-        frame, cam, gs, num_rendered, P, M = ctx.desc
-        p = (xyz, f_dc, opacity, scaling, rotation, f_rest)  # kernel order
-        ws_first = ws if not getattr(ctx, "ws_used", False) else None
-        ctx.ws_used = True
-        st = RawFrame(frame, cam, gs, (tuple(keep), p), radii, geom, img, binning, num_rendered, P, M, ws_first)
-        grads = dict(xyz=torch.empty_like(p[0]), f_dc=torch.empty_like(p[1]), opacity=torch.empty_like(p[2]),
-                     scaling=torch.empty_like(p[3]), rotation=torch.empty_like(p[4]), f_rest=torch.empty_like(p[5]))
-        d2 = torch.empty((st.P, 3), dtype=torch.float32, device=p[0].device)
-        if st.P == 0:
-            d2.zero_()
-        backward(st, grad_color, grads, dmeans2D=d2, dL_ddepth=grad_depth, dL_dalpha=grad_alpha)
-        return (grads["xyz"], grads["f_dc"], grads["f_rest"], grads["opacity"], grads["scaling"], grads["rotation"], d2,
-                None, None, None, None, None, None, None, None, None, None, None)
+        return _raw_backward(ctx, _RAW_INPUTS, grad_color, grad_depth, grad_alpha)
 
 
 class RasterizeRawParamsCamera(torch.autograd.Function):
@@ -486,46 +489,12 @@ class RasterizeRawParamsCamera(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, f_dc, f_rest, opacity, scaling, rotation, means2D, sh_degree, W, H, tanfovx, tanfovy,
                 viewmatrix, projmatrix, campos, bg, low_pass, scale_modifier):
-        viewmatrix, projmatrix, campos = (t.detach().to(torch.float32).contiguous()
-                                          for t in (viewmatrix, projmatrix, campos))
-        ctx.cam_shapes = (viewmatrix.shape, projmatrix.shape, campos.shape)
-        color, radii, depth, st = forward_params((xyz, f_dc, f_rest, opacity, scaling, rotation), sh_degree, W, H,
-                                                 tanfovx, tanfovy, viewmatrix, projmatrix, campos, bg, low_pass,
-                                                 scale_modifier)
-        alpha = accumulated_alpha(st)
-        keep, _p6 = st.keep
-        ctx.save_for_backward(xyz, f_dc, f_rest, opacity, scaling, rotation, st.radii, st.geom, st.img, st.binning,
-                              st.ws, *keep)
-        ctx.desc = (st.frame, st.cam, st.gs, st.num_rendered, st.P, st.M)
-        ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)
-        return color, radii, depth, alpha
+        return _raw_forward(ctx, (xyz, f_dc, f_rest, opacity, scaling, rotation, means2D, sh_degree, W, H, tanfovx,
+                                  tanfovy, viewmatrix, projmatrix, campos, bg, low_pass, scale_modifier), camera=True)
 
     @staticmethod
     def backward(ctx, grad_color, _grad_radii, grad_depth, grad_alpha):
-        if grad_color is None and grad_depth is None and grad_alpha is None:
-            return (None,) * 18
-        xyz, f_dc, f_rest, opacity, scaling, rotation, radii, geom, img, binning, ws, *keep = ctx.saved_tensors
-        frame, cam, gs, num_rendered, P, M = ctx.desc
-        p = (xyz, f_dc, opacity, scaling, rotation, f_rest)  # kernel order
-        ws_first = ws if not getattr(ctx, "ws_used", False) else None
-        ctx.ws_used = True
-        st = RawFrame(frame, cam, gs, (tuple(keep), p), radii, geom, img, binning, num_rendered, P, M, ws_first)
-        grads = dict(xyz=torch.empty_like(p[0]), f_dc=torch.empty_like(p[1]), opacity=torch.empty_like(p[2]),
-                     scaling=torch.empty_like(p[3]), rotation=torch.empty_like(p[4]), f_rest=torch.empty_like(p[5]))
-        d2 = torch.empty((st.P, 3), dtype=torch.float32, device=p[0].device)
-        if st.P == 0:
-            d2.zero_()
-        cg = None
-        if any(ctx.needs_input_grad[12:15]):
-            fo = dict(dtype=torch.float32, device=p[0].device)
-            cg = (torch.empty((4, 4), **fo), torch.empty((4, 4), **fo), torch.empty((3,), **fo))
-        backward(st, grad_color, grads, dmeans2D=d2, dL_ddepth=grad_depth, dL_dalpha=grad_alpha, cam_grads=cg)
-        # (in the inputs' own shapes: a flat [16] matrix gets a flat gradient)
-        d_view, d_proj, d_campos = (g.view(s) for g, s in zip(cg, ctx.cam_shapes)) if cg is not None \
-            else (None, None, None)
-        return (grads["xyz"], grads["f_dc"], grads["f_rest"], grads["opacity"], grads["scaling"], grads["rotation"], d2,
-                None, None, None, None, None, d_view, d_proj, d_campos, None, None, None)
+        return _raw_backward(ctx, _RAW_INPUTS, grad_color, grad_depth, grad_alpha, camera=True)
 
 
 class RasterizeRawParamsNormal(torch.autograd.Function):
@@ -536,37 +505,12 @@ class RasterizeRawParamsNormal(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, f_dc, f_rest, opacity, scaling, rotation, means2D, sh_degree, W, H, tanfovx, tanfovy,
                 viewmatrix, projmatrix, campos, bg, low_pass, scale_modifier):
-        color, radii, depth, st = forward_params((xyz, f_dc, f_rest, opacity, scaling, rotation), sh_degree, W, H,
-                                                 tanfovx, tanfovy, viewmatrix, projmatrix, campos, bg, low_pass,
-                                                 scale_modifier, normal=True)
-        alpha = accumulated_alpha(st)
-        keep, _p6 = st.keep
-        ctx.save_for_backward(xyz, f_dc, f_rest, opacity, scaling, rotation, st.radii, st.geom, st.img, st.binning,
-                              st.ws, *keep)
-        ctx.desc = (st.frame, st.cam, st.gs, st.num_rendered, st.P, st.M)
-        ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)
-        return color, radii, depth, alpha, st.normal
+        return _raw_forward(ctx, (xyz, f_dc, f_rest, opacity, scaling, rotation, means2D, sh_degree, W, H, tanfovx,
+                                  tanfovy, viewmatrix, projmatrix, campos, bg, low_pass, scale_modifier), normal=True)
 
     @staticmethod
     def backward(ctx, grad_color, _grad_radii, grad_depth, grad_alpha, grad_normal):
-        if grad_color is None and grad_depth is None and grad_alpha is None and grad_normal is None:
-            return (None,) * 18
-        xyz, f_dc, f_rest, opacity, scaling, rotation, radii, geom, img, binning, ws, *keep = ctx.saved_tensors
-        frame, cam, gs, num_rendered, P, M = ctx.desc
-        p = (xyz, f_dc, opacity, scaling, rotation, f_rest)  # kernel order
-        ws_first = ws if not getattr(ctx, "ws_used", False) else None
-        ctx.ws_used = True
-        st = RawFrame(frame, cam, gs, (tuple(keep), p), radii, geom, img, binning, num_rendered, P, M, ws_first)
-        grads = dict(xyz=torch.empty_like(p[0]), f_dc=torch.empty_like(p[1]), opacity=torch.empty_like(p[2]),
-                     scaling=torch.empty_like(p[3]), rotation=torch.empty_like(p[4]), f_rest=torch.empty_like(p[5]))
-        d2 = torch.empty((st.P, 3), dtype=torch.float32, device=p[0].device)
-        if st.P == 0:
-            d2.zero_()
-        backward(st, grad_color, grads, dmeans2D=d2, dL_ddepth=grad_depth, dL_dalpha=grad_alpha,
-                 dL_dnormal=grad_normal)
-        return (grads["xyz"], grads["f_dc"], grads["f_rest"], grads["opacity"], grads["scaling"], grads["rotation"], d2,
-                None, None, None, None, None, None, None, None, None, None, None)
+        return _raw_backward(ctx, _RAW_INPUTS, grad_color, grad_depth, grad_alpha, grad_normal)
 
 
 class RasterizeRawParamsDist(torch.autograd.Function):
@@ -578,35 +522,10 @@ class RasterizeRawParamsDist(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, f_dc, f_rest, opacity, scaling, rotation, means2D, sh_degree, W, H, tanfovx, tanfovy,
                 viewmatrix, projmatrix, campos, bg, low_pass, scale_modifier, dist_near, dist_far, normal):
-        color, radii, depth, st = forward_params((xyz, f_dc, f_rest, opacity, scaling, rotation), sh_degree, W, H,
-                                                 tanfovx, tanfovy, viewmatrix, projmatrix, campos, bg, low_pass,
-                                                 scale_modifier, normal=bool(normal), dist=(dist_near, dist_far))
-        alpha = accumulated_alpha(st)
-        keep, _p6 = st.keep
-        ctx.save_for_backward(xyz, f_dc, f_rest, opacity, scaling, rotation, st.radii, st.geom, st.img, st.binning,
-                              st.ws, *keep)
-        ctx.desc = (st.frame, st.cam, st.gs, st.num_rendered, st.P, st.M, st.dist)
-        ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)
-        return color, radii, depth, alpha, st.normal, st.moments
+        return _raw_forward(ctx, (xyz, f_dc, f_rest, opacity, scaling, rotation, means2D, sh_degree, W, H, tanfovx,
+                                  tanfovy, viewmatrix, projmatrix, campos, bg, low_pass, scale_modifier),
+                            normal=bool(normal), dist=(dist_near, dist_far))
 
     @staticmethod
     def backward(ctx, grad_color, _grad_radii, grad_depth, grad_alpha, grad_normal, grad_moments):
-        if all(g is None for g in (grad_color, grad_depth, grad_alpha, grad_normal, grad_moments)):
-            return (None,) * 21
-        xyz, f_dc, f_rest, opacity, scaling, rotation, radii, geom, img, binning, ws, *keep = ctx.saved_tensors
-        frame, cam, gs, num_rendered, P, M, dist = ctx.desc
-        p = (xyz, f_dc, opacity, scaling, rotation, f_rest)  # kernel order
-        ws_first = ws if not getattr(ctx, "ws_used", False) else None
-        ctx.ws_used = True
-        st = RawFrame(frame, cam, gs, (tuple(keep), p), radii, geom, img, binning, num_rendered, P, M, ws_first,
-                      dist=dist)
-        grads = dict(xyz=torch.empty_like(p[0]), f_dc=torch.empty_like(p[1]), opacity=torch.empty_like(p[2]),
-                     scaling=torch.empty_like(p[3]), rotation=torch.empty_like(p[4]), f_rest=torch.empty_like(p[5]))
-        d2 = torch.empty((st.P, 3), dtype=torch.float32, device=p[0].device)
-        if st.P == 0:
-            d2.zero_()
-        backward(st, grad_color, grads, dmeans2D=d2, dL_ddepth=grad_depth, dL_dalpha=grad_alpha,
-                 dL_dnormal=grad_normal, dL_dmoments=grad_moments)
-        return (grads["xyz"], grads["f_dc"], grads["f_rest"], grads["opacity"], grads["scaling"], grads["rotation"], d2,
-                None, None, None, None, None, None, None, None, None, None, None, None, None, None)
+        return _raw_backward(ctx, _RAW_INPUTS + 3, grad_color, grad_depth, grad_alpha, grad_normal, grad_moments)

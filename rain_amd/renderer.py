@@ -109,36 +109,18 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         sh_degree=pc.active_sh_degree, campos=viewpoint_camera.camera_center, prefiltered=False, debug=pipe.debug,
         low_pass=low_pass)
     if raw:
-        from .fused import RasterizeRawParams, RasterizeRawParamsDepth, RasterizeRawParamsNormal
+        from . import fused
 
         raw_args = (pc._xyz, pc._features_dc, pc._features_rest, pc._opacity, pc._scaling, pc._rotation,
                     screenspace_points, pc.active_sh_degree, raster_settings.image_width,
                     raster_settings.image_height, tanfovx, tanfovy, raster_settings.viewmatrix,
                     raster_settings.projmatrix, raster_settings.campos, bg_color, low_pass, scaling_modifier)
         if dist_grad:
-            from .fused import RasterizeRawParamsDist
-
-            rendered_image, radii, depth, alpha, normal, moments = RasterizeRawParamsDist.apply(
-                *raw_args, float(dist_near), float(dist_far), bool(normal_grad))
-            return _dist_package(rendered_image, screenspace_points, radii, depth, alpha, normal, moments)
-        if normal_grad:
-            rendered_image, radii, depth, alpha, normal = RasterizeRawParamsNormal.apply(*raw_args)
-            return {"render": rendered_image, "viewspace_points": screenspace_points,
-                    "visibility_filter": radii > 0, "radii": radii, "depth": depth, "alpha": alpha,
-                    "normal": normal}
-        if pose_grad:
-            from .fused import RasterizeRawParamsCamera
-
-            rendered_image, radii, depth, alpha = RasterizeRawParamsCamera.apply(*raw_args)
-            return {"render": rendered_image, "viewspace_points": screenspace_points,
-                    "visibility_filter": radii > 0, "radii": radii, "depth": depth, "alpha": alpha}
-        if depth_grad:
-            rendered_image, radii, depth, alpha = RasterizeRawParamsDepth.apply(*raw_args)
-            return {"render": rendered_image, "viewspace_points": screenspace_points,
-                    "visibility_filter": radii > 0, "radii": radii, "depth": depth, "alpha": alpha}
-        rendered_image, radii, depth = RasterizeRawParams.apply(*raw_args)
-        return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
-                "radii": radii, "depth": depth}
+            raw_args += (float(dist_near), float(dist_far), bool(normal_grad))
+        fn = (fused.RasterizeRawParamsDist if dist_grad else fused.RasterizeRawParamsNormal if normal_grad
+              else fused.RasterizeRawParamsCamera if pose_grad else fused.RasterizeRawParamsDepth if depth_grad
+              else fused.RasterizeRawParams)
+        return _package(screenspace_points, *fn.apply(*raw_args))
     rasterizer = GaussianRasterizer(raster_settings=raster_settings)
 
     means3D = xyz
@@ -163,42 +145,24 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     else:
         colors_precomp = override_color
 
-    if dist_grad:
-        rendered_image, radii, depth, alpha, normal, moments = rasterizer.forward_distortion(
-            means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors_precomp, opacities=opacity,
-            scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp, dist_near=dist_near, dist_far=dist_far,
-            normal=normal_grad)
-        return _dist_package(rendered_image, screenspace_points, radii, depth, alpha, normal, moments)
-    if normal_grad:
-        rendered_image, radii, depth, alpha, normal = rasterizer.forward_normal(
-            means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors_precomp, opacities=opacity,
-            scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp)
-        return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
-                "radii": radii, "depth": depth, "alpha": alpha, "normal": normal}
-    if pose_grad:
-        rendered_image, radii, depth, alpha = rasterizer.forward_camera(
-            means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors_precomp, opacities=opacity,
-            scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp)
-        return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
-                "radii": radii, "depth": depth, "alpha": alpha}
-    if depth_grad:
-        rendered_image, radii, depth, alpha = rasterizer.forward_depth(
-            means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors_precomp, opacities=opacity,
-            scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp)
-        return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
-                "radii": radii, "depth": depth, "alpha": alpha}
-    rendered_image, radii, depth = rasterizer(means3D=means3D, means2D=means2D, shs=shs,
-                                              colors_precomp=colors_precomp, opacities=opacity, scales=scales,
-                                              rotations=rotations, cov3D_precomp=cov3D_precomp)
-    return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
-            "radii": radii, "depth": depth}
+    forward = (rasterizer.forward_distortion if dist_grad else rasterizer.forward_normal if normal_grad
+               else rasterizer.forward_camera if pose_grad else rasterizer.forward_depth if depth_grad else rasterizer)
+    extra = dict(dist_near=dist_near, dist_far=dist_far, normal=normal_grad) if dist_grad else {}
+    return _package(screenspace_points, *forward(means3D=means3D, means2D=means2D, shs=shs,
+                                                 colors_precomp=colors_precomp, opacities=opacity, scales=scales,
+                                                 rotations=rotations, cov3D_precomp=cov3D_precomp, **extra))
 
 
-def _dist_package(rendered_image, screenspace_points, radii, depth, alpha, normal, moments):
-    """render(dist_grad=True)'s dictionary ("normal" only with normal_grad)."""
+def _package(screenspace_points, rendered_image, radii, depth, alpha=None, normal=None, moments=None):
+    """render()'s dictionary from the rasterizer's output tuple: the reference's five entries, then "alpha",
+    "normal", "depth_moments" and "distortion" for the maps the chosen mode rendered."""
     pkg = {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
-           "radii": radii, "depth": depth, "alpha": alpha, "depth_moments": moments,
-           "distortion": alpha * moments[1:2] - moments[0:1] * moments[0:1]}
+           "radii": radii, "depth": depth}
+    if alpha is not None:
+        pkg["alpha"] = alpha
+    if moments is not None:
+        pkg["depth_moments"] = moments
+        pkg["distortion"] = alpha * moments[1:2] - moments[0:1] * moments[0:1]
     if normal is not None:
         pkg["normal"] = normal
     return pkg
