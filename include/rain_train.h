@@ -132,6 +132,89 @@ int rt_densify_stats(int P, const float* grad2d, int grad_stride, const uint8_t*
                      float* denom, void* stream);
 int rt_max_radii(int P, const int* radii, const uint8_t* vis, float* max_radii2D, void* stream);
 
+/*
+ * MCMC densification ("3D Gaussian Splatting as Markov Chain Monte Carlo", Kheradmand et al.,
+ * NeurIPS 2024; rain_amd/csrc/mcmc.hip, rain_amd/mcmc.py).  Parameters are GaussianModel's RAW
+ * tensors: logit opacity [P,1], log scale [P,3], unnormalised quaternion [P,4] (w,x,y,z), xyz [P,3],
+ * f_dc [P,1,3], f_rest [P,M-1,3].
+ *
+ * rt_mcmc_relocate: for every pair j, row dst[j] of every group becomes a copy of row src[j], in
+ * place.  src / dst are row indices in [0, P), int64 as torch.multinomial returns them; src may
+ * repeat.  PRECONDITIONS the caller guarantees (the kernels cannot check them): dst has no
+ * duplicates, and no row is both a source and a destination.  A pair with an index outside [0, P)
+ * is skipped, never dereferenced.
+ * With c_i = #{j : src[j] == i} (integer atomics: deterministic), a source i has
+ *   N = min(c_i + 1, RT_MCMC_N_MAX),  o = sigmoid(opacity_i),  o' = 1 - (1 - o)^(1/N),
+ *   D = sum_{a=1..N} sum_{k=0..a-1} C(a-1,k) (-1)^k o'^(k+1) / sqrt(k+1),  coeff = o / D,
+ *   opacity_new = logit(clamp(o', min_opacity, 1 - FLT_EPSILON)),  scaling_new = scaling_i + log(coeff)
+ * (all three axes); o', D and coeff are formed in double (the sum alternates and cancels: fp32
+ * reaches 2e-4 relative at o -> 1, N = 51; fp64 stays within 1e-13).  N = 1 gives o' = o, coeff = 1.
+ * Two passes in stream order: (1) per pair, row dst[j] <- row src[j] read with its OLD values, its
+ * opacity and scaling replaced by the source's new values, its moments set to 0; (2) per source
+ * with c_i > 0, its own opacity and scaling take the same new values and its moments are set to 0 in
+ * ALL groups.  This deviates from gsplat's MCMCStrategy, which clears the moments of the sources
+ * only: here a relocated row is a new Gaussian and keeps no stale momentum either.  Rows that are
+ * neither a source nor a destination are bitwise unchanged; n == 0 launches nothing.
+ * Errors: 1 for an argument error (before any device work), 3 for too small a workspace
+ * (rt_mcmc_workspace_bytes(P): the per-row source counts).
+ */
+#define RT_MCMC_N_MAX 51
+#define RT_GROUP_OPACITY 3               /* beside RT_GROUP_OTHER / XYZ / SCALING */
+typedef struct rt_mcmc_group {           /* updated IN PLACE */
+    float* param;                        /* [P, width] */
+    float* exp_avg;                      /* [P, width], or NULL with exp_avg_sq: no optimizer state yet */
+    float* exp_avg_sq;
+    int width;
+    int kind;                            /* RT_GROUP_*; one OPACITY (width 1) and one SCALING group are required */
+} rt_mcmc_group;
+
+size_t rt_mcmc_workspace_bytes(int P);
+int rt_mcmc_relocate(int P, const int64_t* src, const int64_t* dst, int n, float min_opacity,
+                     const rt_mcmc_group* groups, int n_groups, void* workspace, size_t workspace_bytes,
+                     void* stream);
+
+/*
+ * rt_mcmc_step: the MCMC iteration's optimizer block for the four geometry groups in ONE launch.
+ * Per row, in this order:
+ *  1. regulariser gradients of lambda_o * mean(sigmoid(opacity)) and lambda_s * mean(exp(scaling)),
+ *     added in registers (the gradient arrays are read only), from the values BEFORE the update:
+ *       g_opacity    += (float)(lambda_o / P)     * s (1 - s),  s = sigmoid(opacity)
+ *       g_scaling[c] += (float)(lambda_s / (3 P)) * exp(scaling[c])
+ *     a zero weight adds nothing (the term is not evaluated);
+ *  2. if do_adam: rt_adam_step's update of the four groups (the same inline arithmetic; with both
+ *     weights 0 and no noise the result is bitwise rt_adam_step's);
+ *  3. if noise: with the UPDATED opacity, scaling and rotation,
+ *       gate = 1 / (1 + exp(gate_k * (sigmoid(opacity) - gate_x0)))   (an overflowing exp gives 0)
+ *       Sigma = R diag(exp(scaling)^2) R^T,  R the rotation of the normalised quaternion
+ *       xyz += Sigma * (noise_row * gate * (float)noise_scale).
+ * The SH groups are stepped by the caller with rt_adam_step.  P == 0 launches nothing.
+ * Errors (1, before any device work): null args, P < 0, a negative weight, with do_adam a null
+ * param / grad / moment in any group, without do_adam a null param in any group when noise is given.
+ */
+typedef struct rt_mcmc_step_group {      /* as rt_adam_group, numel implied by P */
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    double lr;
+    float bias_correction1;
+    float bias_correction2_sqrt;
+} rt_mcmc_step_group;
+
+typedef struct rt_mcmc_step_args {
+    int P;
+    rt_mcmc_step_group xyz, opacity, scaling, rotation;   /* widths 3, 1, 3, 4 */
+    double beta1, beta2, eps;
+    int do_adam;            /* 0: parameters and moments untouched by Adam (noise only) */
+    double opacity_reg;     /* lambda_o; 0: term not evaluated */
+    double scale_reg;       /* lambda_s; 0: term not evaluated */
+    const float* noise;     /* [P,3] standard normals drawn by the caller, or NULL: no noise */
+    double noise_scale;     /* noise_lr * the xyz group's current lr */
+    float gate_k, gate_x0;  /* 100, 0.005 */
+} rt_mcmc_step_args;
+
+int rt_mcmc_step(const rt_mcmc_step_args* a, void* stream);
+
 /* Trace markers (not on the training path): launches an empty one-wave kernel named
  * k_trace_mark_begin (which == 0) or k_trace_mark_end (which != 0) on `stream`, so that a
  * rocprofv3 kernel trace can be cut to the launches between them (bench.py's timed loop). */

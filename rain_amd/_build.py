@@ -28,7 +28,7 @@ LIBS = {
                           "rr_sort.hip", "rr_contrib.hip", "rr_api.hip"],
     "librain_loss.so": ["loss.hip", "geom_loss.hip"],
     "librain_knn.so": ["knn.hip"],
-    "librain_train.so": ["train.hip", "densify.hip"],
+    "librain_train.so": ["train.hip", "densify.hip", "mcmc.hip"],
 }
 
 

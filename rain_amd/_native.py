@@ -278,7 +278,7 @@ def loss_lib():
 TRAIN_LIB = os.path.join(LIB_DIR, "librain_train.so")
 TRAIN_SYMBOLS = ["rt_adam_step", "rt_adam_step_scaled", "rt_densify_workspace_bytes", "rt_densify_plan",
                  "rt_densify_apply", "rt_stream_copy", "rt_stream_rmw", "rt_trace_marker", "rt_densify_stats",
-                 "rt_max_radii", "rt_last_error"]
+                 "rt_max_radii", "rt_last_error", "rt_mcmc_workspace_bytes", "rt_mcmc_relocate", "rt_mcmc_step"]
 RT_MAX_GROUPS = 8
 _train = None
 
@@ -303,6 +303,31 @@ class RTAdamGroup(ctypes.Structure):
     _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p),
                 ("exp_avg_sq", ctypes.c_void_p), ("numel", ctypes.c_int64), ("lr", ctypes.c_double),
                 ("bias_correction1", ctypes.c_float), ("bias_correction2_sqrt", ctypes.c_float)]
+
+
+RT_GROUP_OPACITY = 3
+RT_MCMC_N_MAX = 51
+
+
+class RTMcmcGroup(ctypes.Structure):
+    """include/rain_train.h rt_mcmc_group: one parameter group of rt_mcmc_relocate, updated in place."""
+    _fields_ = [("param", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p), ("exp_avg_sq", ctypes.c_void_p),
+                ("width", ctypes.c_int), ("kind", ctypes.c_int)]
+
+
+class RTMcmcStepGroup(ctypes.Structure):
+    _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p),
+                ("exp_avg_sq", ctypes.c_void_p), ("lr", ctypes.c_double), ("bias_correction1", ctypes.c_float),
+                ("bias_correction2_sqrt", ctypes.c_float)]
+
+
+class RTMcmcStepArgs(ctypes.Structure):
+    """include/rain_train.h rt_mcmc_step_args."""
+    _fields_ = [("P", ctypes.c_int)] + [(n, RTMcmcStepGroup) for n in ("xyz", "opacity", "scaling", "rotation")] + \
+               [("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
+                ("do_adam", ctypes.c_int), ("opacity_reg", ctypes.c_double), ("scale_reg", ctypes.c_double),
+                ("noise", ctypes.c_void_p), ("noise_scale", ctypes.c_double), ("gate_k", ctypes.c_float),
+                ("gate_x0", ctypes.c_float)]
 
 
 def train_lib():
@@ -336,6 +361,15 @@ def train_lib():
         L.rt_max_radii.restype = ctypes.c_int
         L.rt_max_radii.argtypes = [ctypes.c_int, vp, vp, vp, vp]
         L.rt_last_error.restype = ctypes.c_char_p
+        # MCMC densification (rain_amd/csrc/mcmc.hip): P, src, dst, n, min_opacity, groups, n_groups,
+        # workspace, workspace_bytes, stream
+        L.rt_mcmc_workspace_bytes.restype = ctypes.c_size_t
+        L.rt_mcmc_workspace_bytes.argtypes = [ctypes.c_int]
+        L.rt_mcmc_relocate.restype = ctypes.c_int
+        L.rt_mcmc_relocate.argtypes = [ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_float,
+                                       ctypes.POINTER(RTMcmcGroup), ctypes.c_int, vp, ctypes.c_size_t, vp]
+        L.rt_mcmc_step.restype = ctypes.c_int
+        L.rt_mcmc_step.argtypes = [ctypes.POINTER(RTMcmcStepArgs), vp]
         _train = L
     return _train
 

@@ -116,6 +116,17 @@ class OptimizationParams:
         self.importance_prune_iterations = ()
         self.importance_prune_fraction = 0.0
         self.importance_prune_kind = "weight_volume"
+        # opt-in (no reference counterpart): how the set of Gaussians evolves.  "default": the
+        # reference's clone / split / prune and opacity reset.  "mcmc" (rain_amd.mcmc): dead Gaussians
+        # are relocated onto live ones and the set grows by 5 % per densification event up to `cap_max`
+        # (required > 0), with L1 regularisers on opacity and scale and a position noise of
+        # noise_lr * lr_xyz; the last four fields are read only under "mcmc"
+        self.densify_strategy = "default"
+        self.cap_max = 0
+        self.noise_lr = 5e5
+        self.opacity_reg = 0.01
+        self.scale_reg = 0.01
+        self.mcmc_min_opacity = 0.005
         for k, v in kw.items():
             setattr(self, k, v)
 
@@ -610,6 +621,20 @@ class GaussianModel:
         self.denom = torch.zeros((Pn, 1), device=dev)
         self.max_radii2D = torch.zeros((Pn,), device=dev)
         self.flat_grad = None
+
+    # ---- MCMC densification (rain_amd/mcmc.py), under the names 3dgs-mcmc's users look for ----
+    def relocate_gs(self, min_opacity=0.005, generator=None):
+        """Relocate the dead Gaussians (sigmoid(opacity) <= min_opacity) onto live ones, in place
+        (rain_amd.mcmc.relocate_dead).  Returns the number relocated."""
+        from . import mcmc
+
+        return mcmc.relocate_dead(self, min_opacity=min_opacity, generator=generator)
+
+    def add_new_gs(self, cap_max, generator=None, min_opacity=0.005):
+        """Grow the set by 5 %, at most to `cap_max` (rain_amd.mcmc.add_new).  Returns the number added."""
+        from . import mcmc
+
+        return mcmc.add_new(self, cap_max, generator=generator, min_opacity=min_opacity)
 
     def add_densification_stats(self, viewspace_point_tensor, update_filter):
         """gaussian_model.py:419-421 (consumes the NDC-space dL/dmeans2D the rasterizer returns).

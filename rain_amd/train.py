@@ -237,6 +237,31 @@ class Trainer:
         self._geometry_weight(0)  # a non-zero lambda_normal on the sharded paths is refused here already
         self._distortion_weight(0)  # and so is a non-zero lambda_dist
         self._importance_prune_now(0)  # and importance pruning
+        self.noise_gen = None
+        if self._mcmc():  # (checks the options it does not combine with)
+            self.noise_gen = torch.Generator(device=dev).manual_seed(self.cfg.seed + 54321)
+
+    def _mcmc(self) -> bool:
+        """Whether OptimizationParams.densify_strategy selects the MCMC step (rain_amd/mcmc.py); refuses an
+        unknown strategy, a missing cap and the options that step does not carry yet."""
+        opt = self.opt
+        strategy = getattr(opt, "densify_strategy", "default")
+        if strategy == "default":
+            return False
+        if strategy != "mcmc":
+            raise ValueError(f"densify_strategy must be 'default' or 'mcmc', got {strategy!r}")
+        if int(getattr(opt, "cap_max", 0) or 0) <= 0:
+            raise ValueError("densify_strategy 'mcmc' needs cap_max > 0: the number of Gaussians the set grows to")
+        if self.sharded:
+            raise ValueError("densify_strategy 'mcmc' needs the single-GPU step: the Gaussian-sharded / multi-rank "
+                             "steps have no relocation or noise step; train on one GPU or use the default strategy")
+        if any(float(getattr(opt, k, 0.0) or 0.0) != 0.0 for k in ("lambda_normal", "lambda_dist")):
+            raise ValueError("densify_strategy 'mcmc' does not combine with lambda_normal / lambda_dist yet: its step "
+                             "renders the colour image only; set both to 0")
+        if tuple(getattr(opt, "importance_prune_iterations", ()) or ()):
+            raise ValueError("densify_strategy 'mcmc' does not combine with importance_prune_iterations yet: the "
+                             "set is bounded by cap_max; leave it empty")
+        return True
 
     def _low_pass_and_view(self, iteration):
         g, opt, cfg = self.g, self.opt, self.cfg
@@ -355,6 +380,8 @@ class Trainer:
         return float(getattr(self.opt, "dist_near", 0.2)), float(getattr(self.opt, "dist_far", 100.0))
 
     def step(self, iteration: int, sync_loss: bool = False) -> StepInfo:
+        if self._mcmc():
+            return self._step_mcmc(iteration, sync_loss)
         if self.fused:
             return self._step_fused(iteration, sync_loss)
         return self._step_autograd(iteration, sync_loss)
@@ -611,3 +638,49 @@ class Trainer:
             self._importance_prune()
         return StepInfo(loss=float(loss.item()) if sync_loss else None, num_gaussians=g.get_xyz.shape[0],
                         view=vidx, low_pass=self.low_pass, densified=densified)
+
+    def _step_mcmc(self, iteration: int, sync_loss: bool = False) -> StepInfo:
+        """The step under densify_strategy "mcmc" (rain_amd/mcmc.py), single GPU or CPU: the schedule of
+        the default step, the colour loss's gradients (HIP: the fused forward / loss / backward into the
+        flat gradient buffer, no densification statistics; otherwise render() + autograd), then on a
+        densification event the relocation of the dead Gaussians and the growth towards cap_max, and
+        the optimizer block: regularisers + Adam + position noise.  An event replaces or rewrites
+        parameters before the optimizer runs, so, as on the default step's densify iterations, its Adam
+        update is skipped (step counts stay) and only the noise is applied.  No opacity reset ever runs."""
+        from . import mcmc
+
+        g, opt, cfg = self.g, self.opt, self.cfg
+        vidx, cam = self._low_pass_and_view(iteration)
+        event = (cfg.densify and opt.densify_from_iter < iteration < opt.densify_until_iter
+                 and iteration % opt.densification_interval == 0)
+        gt = self.gt[vidx]
+        if self.fused:
+            from . import fused
+            from .loss import l1_ssim_forward_backward
+
+            if self._bin_cache is None:
+                self._bin_cache = fused.BinningCache()
+            g.bind_flat_grad(zero=False)  # the backward overwrites every gradient
+            grads = dict(xyz=g._xyz.grad, f_dc=g._features_dc.grad, f_rest=g._features_rest.grad,
+                         opacity=g._opacity.grad, scaling=g._scaling.grad, rotation=g._rotation.grad)
+            with torch.no_grad():
+                image, _radii, _depth, st = fused.forward(g, cam, self.background, self.low_pass,
+                                                          cache=self._bin_cache if self.reuse_binning else None)
+                loss, _parts, dimg = l1_ssim_forward_backward(image, gt, opt.lambda_dssim)
+                fused.backward(st, dimg, grads, None)
+        else:
+            for p in g.params():
+                p.grad = None
+            pkg = render(cam, g, self.pipe, self.background, low_pass=self.low_pass)
+            loss = self.loss_fn(pkg["render"], gt, opt.lambda_dssim)
+            loss.backward()
+        with torch.no_grad():
+            if event:
+                mcmc.relocate_dead(g, opt.mcmc_min_opacity, generator=self.densify_gen)
+                mcmc.add_new(g, opt.cap_max, generator=self.densify_gen, min_opacity=opt.mcmc_min_opacity)
+            if iteration < opt.iterations:
+                noise = torch.randn((g.get_xyz.shape[0], 3), device=g.get_xyz.device, generator=self.noise_gen)
+                mcmc.step(g, noise, opt.noise_lr, opt.opacity_reg, opt.scale_reg, do_adam=not event)
+            g.optimizer.zero_grad(set_to_none=True)
+        return StepInfo(loss=float(loss.item()) if sync_loss else None, num_gaussians=g.get_xyz.shape[0],
+                        view=vidx, low_pass=self.low_pass, densified=bool(event))

@@ -1,0 +1,196 @@
+"""CPU checks of the MCMC densification surface: librain_train.so exports, declares and binds rt_mcmc_*, the
+ctypes structs have the header's sizes, every argument error comes back non-zero with a message before any
+device work (the pointers below are stand-ins, so a call that got past validation would fault), empty calls
+succeed, OptimizationParams has the documented defaults and Trainer refuses what the MCMC step does not carry."""
+import ctypes
+import inspect
+import os
+
+import pytest
+import torch
+
+from rain_amd import _native as N
+from rain_amd import cameras, mcmc, synthetic
+from rain_amd.gaussian_model import GaussianModel, OptimizationParams
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_symbols_exported_declared_and_bound():
+    so = ctypes.CDLL(N.TRAIN_LIB)
+    header = open(os.path.join(ROOT, "include", "rain_train.h")).read()
+    for name in ("rt_mcmc_workspace_bytes", "rt_mcmc_relocate", "rt_mcmc_step"):
+        assert hasattr(so, name), f"librain_train.so does not export {name}"
+        assert name in N.TRAIN_SYMBOLS and name + "(" in header
+    assert "#define RT_MCMC_N_MAX 51" in header and "#define RT_GROUP_OPACITY 3" in header
+    assert (N.RT_MCMC_N_MAX, N.RT_GROUP_OPACITY) == (51, 3)
+    assert "clears the moments of the sources\n * only" in header  # the deviation from gsplat is documented
+    # the sizes mcmc.hip static_asserts for the C structs
+    assert ctypes.sizeof(N.RTMcmcGroup) == 32
+    assert ctypes.sizeof(N.RTMcmcStepGroup) == 48
+    assert ctypes.sizeof(N.RTMcmcStepArgs) == 272
+    assert [f[0] for f in N.RTMcmcGroup._fields_] == ["param", "exp_avg", "exp_avg_sq", "width", "kind"]
+    assert [f[0] for f in N.RTMcmcStepArgs._fields_] == [
+        "P", "xyz", "opacity", "scaling", "rotation", "beta1", "beta2", "eps", "do_adam", "opacity_reg",
+        "scale_reg", "noise", "noise_scale", "gate_k", "gate_x0"]
+    L = N.train_lib()
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    assert list(L.rt_mcmc_relocate.argtypes) == [ci, vp, vp, ci, ctypes.c_float, ctypes.POINTER(N.RTMcmcGroup), ci, vp,
+                                                 ctypes.c_size_t, vp]
+    assert list(L.rt_mcmc_step.argtypes) == [ctypes.POINTER(N.RTMcmcStepArgs), vp]
+    assert L.rt_mcmc_workspace_bytes(0) > 0
+    assert 4 * 1000 <= L.rt_mcmc_workspace_bytes(1000) < L.rt_mcmc_workspace_bytes(1_000_000) <= 4 * 1_000_000 + 256
+
+
+def _groups(op_kind=N.RT_GROUP_OPACITY, sc_kind=N.RT_GROUP_SCALING, **kw):
+    g = [N.RTMcmcGroup(16, 16, 16, 3, N.RT_GROUP_XYZ), N.RTMcmcGroup(16, 16, 16, 1, op_kind),
+         N.RTMcmcGroup(16, 16, 16, 3, sc_kind), N.RTMcmcGroup(16, None, None, 45, N.RT_GROUP_OTHER)]
+    for k, v in kw.items():
+        i, field = k.split("_", 1)
+        setattr(g[int(i[1:])], field, v)
+    return (N.RTMcmcGroup * len(g))(*g), len(g)
+
+
+def test_rt_mcmc_relocate_validation_without_gpu():
+    L = N.train_lib()
+    ws_bytes = L.rt_mcmc_workspace_bytes(100)
+    base = dict(P=100, src=16, dst=16, n=5, min_opacity=0.005, groups=_groups(), ws=16, ws_bytes=ws_bytes)
+
+    def call(**kw):
+        a = dict(base, **kw)
+        arr, ng = a["groups"] if a["groups"] is not None else (None, 0)
+        return L.rt_mcmc_relocate(a["P"], a["src"], a["dst"], a["n"], a["min_opacity"], arr, ng, a["ws"],
+                                  a["ws_bytes"], None)
+
+    def err():
+        return L.rt_last_error()
+
+    assert call(groups=None) == 1 and b"null groups" in err()
+    assert call(ws=None) == 1 and b"null workspace" in err()
+    assert call(src=None) == 1 and b"null src / dst" in err()
+    assert call(dst=None) == 1 and b"null src / dst" in err()
+    assert call(P=-1) == 1 and b"negative P / n" in err()
+    assert call(n=-1) == 1 and b"negative P / n" in err()
+    assert call(groups=_groups(g0_param=None)) == 1 and b"null param or width <= 0" in err()
+    assert call(groups=_groups(g3_width=0)) == 1 and b"null param or width <= 0" in err()
+    assert call(groups=_groups(g2_width=-3)) == 1 and b"null param or width <= 0" in err()
+    assert call(groups=_groups(op_kind=N.RT_GROUP_OTHER)) == 1 and b"no group of kind OPACITY or SCALING" in err()
+    assert call(groups=_groups(sc_kind=N.RT_GROUP_OTHER)) == 1 and b"no group of kind OPACITY or SCALING" in err()
+    assert call(groups=_groups(g1_exp_avg=None)) == 1 and b"moments" in err()
+    for bad in (0.0, 1.0, -0.1, 1.5, float("nan")):
+        assert call(min_opacity=bad) == 1 and b"min_opacity must be in (0, 1)" in err(), bad
+    assert call(ws_bytes=ws_bytes - 1) == 3 and b"workspace too small" in err()
+    # n == 0 launches nothing, whatever the buffers are; so does P == 0 (every index is out of range)
+    assert call(n=0, src=None, dst=None, groups=None, ws=None, ws_bytes=0) == 0
+    assert call(n=0) == 0
+    assert call(P=0) == 0
+
+
+def _step_args(**kw):
+    a = N.RTMcmcStepArgs()
+    a.P = 100
+    for name in ("xyz", "opacity", "scaling", "rotation"):
+        g = getattr(a, name)
+        g.param, g.grad, g.exp_avg, g.exp_avg_sq = 16, 16, 16, 16
+        g.lr, g.bias_correction1, g.bias_correction2_sqrt = 1e-3, 0.1, 0.03
+    a.beta1, a.beta2, a.eps = 0.9, 0.999, 1e-15
+    a.do_adam, a.opacity_reg, a.scale_reg = 1, 0.01, 0.01
+    a.noise, a.noise_scale, a.gate_k, a.gate_x0 = 16, 1.0, 100.0, 0.005
+    for k, v in kw.items():
+        if "__" in k:
+            grp, field = k.split("__")
+            setattr(getattr(a, grp), field, v)
+        else:
+            setattr(a, k, v)
+    return a
+
+
+def test_rt_mcmc_step_validation_without_gpu():
+    L = N.train_lib()
+
+    def call(**kw):
+        return L.rt_mcmc_step(ctypes.byref(_step_args(**kw)), None)
+
+    def err():
+        return L.rt_last_error()
+
+    assert L.rt_mcmc_step(None, None) == 1 and b"null args" in err()
+    assert call(P=-1) == 1 and b"negative P" in err()
+    for grp in ("xyz", "opacity", "scaling", "rotation"):
+        for field in ("param", "grad", "exp_avg", "exp_avg_sq"):
+            assert call(**{f"{grp}__{field}": None}) == 1 and b"null param / grad / moment" in err(), (grp, field)
+        # noise only: the parameters are still needed, gradients and moments are not
+        assert call(do_adam=0, **{f"{grp}__param": None}) == 1 and b"null param in a group" in err(), grp
+    assert call(opacity_reg=-0.01) == 1 and b"negative regulariser weight" in err()
+    assert call(scale_reg=-1e-9) == 1 and b"negative regulariser weight" in err()
+    assert call(P=0) == 0
+    assert call(P=0, do_adam=0, noise=None) == 0
+    # nothing to do: no Adam, no noise -> no launch, whatever the group pointers are
+    assert call(do_adam=0, noise=None, xyz__param=None, opacity__param=None) == 0
+
+
+def test_optimization_params_defaults_and_python_surface():
+    opt = OptimizationParams()
+    assert (opt.densify_strategy, opt.cap_max, opt.noise_lr, opt.opacity_reg, opt.scale_reg, opt.mcmc_min_opacity) == \
+        ("default", 0, 5e5, 0.01, 0.01, 0.005)
+    assert OptimizationParams(densify_strategy="mcmc", cap_max=7).cap_max == 7
+    sig = inspect.signature(mcmc.relocation_values).parameters
+    assert list(sig) == ["opacity", "scale", "ratio"]
+    sig = inspect.signature(mcmc.relocate_dead).parameters
+    assert list(sig) == ["model", "min_opacity", "generator"] and sig["min_opacity"].default == 0.005
+    sig = inspect.signature(mcmc.add_new).parameters
+    assert list(sig)[:3] == ["model", "cap_max", "generator"] and sig["generator"].default is None
+    sig = inspect.signature(mcmc.step).parameters
+    assert list(sig) == ["model", "noise", "noise_lr", "opacity_reg", "scale_reg", "do_adam"]
+    assert sig["do_adam"].default is True
+    assert callable(GaussianModel.relocate_gs) and callable(GaussianModel.add_new_gs)
+    assert mcmc.N_MAX == 51 and (mcmc.GATE_K, mcmc.GATE_X0) == (100.0, 0.005)
+
+
+def test_multinomial_limit_is_a_value_error():
+    class Big:  # a stand-in with more rows than torch.multinomial takes; nothing is allocated per row
+        _opacity = torch.zeros(1).expand((1 << 24) + 1, 1)
+        _xyz = torch.zeros(1, 3).expand((1 << 24) + 1, 3)
+
+    with pytest.raises(ValueError, match="at most 2\\^24 categories"):
+        mcmc.add_new(Big(), cap_max=1 << 26)
+
+
+def _ref_loss(img, gt, lam):
+    return (img - gt).abs().mean()
+
+
+def _trainer(**kw):
+    from rain_amd.renderer import PipelineParams
+    from rain_amd.train import TrainConfig, Trainer
+
+    g = GaussianModel(1, divide_ratio=0.8, device="cpu")
+    g.set_params(synthetic.random_gaussians(50, sh_degree=1, seed=0, bench=True))
+    g.spatial_lr_scale = 4.4
+    opt = OptimizationParams(**kw)
+    g.training_setup(opt)
+    cams = cameras.fibonacci_cameras(4, 32, 24)
+    gts = [torch.zeros(3, 24, 32) for _ in cams]
+    return Trainer(g, cams, gts, opt, PipelineParams(), TrainConfig(c2f=False), scene_extent=4.4, loss_fn=_ref_loss)
+
+
+def test_trainer_refusals():
+    with pytest.raises(ValueError, match="needs cap_max > 0"):
+        _trainer(densify_strategy="mcmc")
+    with pytest.raises(ValueError, match="needs cap_max > 0"):
+        _trainer(densify_strategy="mcmc", cap_max=-5)
+    with pytest.raises(ValueError, match="must be 'default' or 'mcmc'"):
+        _trainer(densify_strategy="adc")
+    with pytest.raises(ValueError, match="lambda_normal / lambda_dist"):
+        _trainer(densify_strategy="mcmc", cap_max=60, lambda_normal=0.05)
+    with pytest.raises(ValueError, match="lambda_normal / lambda_dist"):
+        _trainer(densify_strategy="mcmc", cap_max=60, lambda_dist=100.0)
+    with pytest.raises(ValueError, match="importance_prune_iterations"):
+        _trainer(densify_strategy="mcmc", cap_max=60, importance_prune_iterations=(6,), importance_prune_fraction=0.3)
+    t = _trainer(densify_strategy="mcmc", cap_max=60)
+    assert t.noise_gen is not None and not t.sharded
+    t.sharded = True  # what world > 1 (or a forced exchange) sets; no ranks are started
+    with pytest.raises(ValueError, match="'mcmc' needs the single-GPU step"):
+        t.step(1)
+    t0 = _trainer()  # the default strategy: no MCMC state, cap_max unread
+    assert t0.noise_gen is None and not t0._mcmc()
