@@ -62,7 +62,18 @@ using rl_detail::g_err;
 
 struct Win {
     float w[11];
+    float delta;  // (sum w)^2 - 1: how far the 2-D window's sum is from 1 (host, in double)
 };
+Win make_win(const float* window) {
+    Win win;
+    double sw = 0.0;
+    for (int i = 0; i < 11; i++) {
+        win.w[i] = window[i];
+        sw += (double)window[i];
+    }
+    win.delta = (float)(sw * sw - 1.0);
+    return win;
+}
 
 // 1/x: v_rcp_f32 (1 ulp) plus one Newton step
 __device__ __forceinline__ float rcp_nr(float x) {
@@ -111,13 +122,16 @@ struct PatchRow {
             for (int k = 0; k < NP; k++)
                 v[k][h] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs[k], voff[h], soff, 0));
     }
+    // The backward's three planes (NP == 3: G1, G11, G12) go to LDS as G1, G11, G12 + 2 G11: see
+    // k_ssim_bwd for why the third plane is blurred in that form.
     __device__ __forceinline__ void store(float (*dst)[NR][PW], int slot, int lane) const {
 #pragma unroll
         for (int h = 0; h < NQ; h++) {
             const int q = lane + 64 * h;
             if (q < PW)
 #pragma unroll
-                for (int k = 0; k < NP; k++) dst[k][slot][q] = v[k][h];
+                for (int k = 0; k < NP; k++)
+                    dst[k][slot][q] = (NP == 3 && k == 2) ? __builtin_fmaf(2.f, v[1][h], v[NP - 1][h]) : v[k][h];
         }
     }
 };
@@ -194,6 +208,27 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void k_
     const int vo = col_in ? 4 * gx : kOOB;
     const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
     const float k = -lambda * inv_n;
+    // The second moments are taken about a per-lane origin (cx, cy) = the two images at this column
+    // in the tile's middle row (scaled, below): E[x^2] - m^2 of a smooth or constant image is then a difference of
+    // small numbers instead of a cancellation of O(1) terms against C2 = 9e-4 (which every pixel
+    // of such an image rounds alike, so that the mean SSIM was off by 1e-5).  Zero-padded taps
+    // count as -c, so the window's sum W = 1 + delta is the same at every pixel, and with
+    // m' = m - c W:  E[xy] - m1 m2 = (E'[xy] - m1' m2') - delta (cy m1 + cx m2 - cx cy W).
+    // The origin is scaled by the window's mass inside the image there (zero padding pulls the
+    // window's mean towards 0: in a one-row image 73% of every window is padding).
+    const int mid = min((int)blockIdx.y * TH + TH / 2, H - 1);
+    float mh = 0.f, mv = 0.f;
+#pragma unroll
+    for (int j = 0; j < 11; j++) {
+        mh += (gx - R + j >= 0 && gx - R + j < W) ? win.w[j] : 0.f;
+        mv += (mid - R + j >= 0 && mid - R + j < H) ? win.w[j] : 0.f;
+    }
+    // Below half the mass inside, no shift: it would gain less than a factor 2 on the second
+    // moments and cost m = m' + c W a rounding (in a 1x1 image m' is nothing but rounding).
+    const float mass = mh * mv >= 0.5f ? mh * mv : 0.f;
+    const float cx = mass * load_f32(rs[0], vo, mid * 4 * W);
+    const float cy = mass * load_f32(rs[1], vo, mid * 4 * W);
+    const float dl = win.delta;
     float r0[11], r1[11], r2[11], r3[11], r4[11];  // register ring, one array per moment
     float s_val = 0.f, l1 = 0.f;
 #pragma unroll
@@ -205,7 +240,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void k_
         float a = 0.f, b = 0.f, aa = 0.f, bb = 0.f, ab = 0.f;
 #pragma unroll
         for (int j = 0; j < 11; j++) {
-            const float xv = px[j], yv = py[j], wj = win.w[j];
+            const float xv = px[j] - cx, yv = py[j] - cy, wj = win.w[j];
             a += wj * xv;
             b += wj * yv;
             aa += wj * (xv * xv);
@@ -229,21 +264,24 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void k_
         r4[r % 11] = ab;
         if (r >= 2 * R) {
             const int o = r - 2 * R;  // output row within the tile
-            float m1 = 0.f, m2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
+            float m1p = 0.f, m2p = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
 #pragma unroll
             for (int i = 0; i < 11; i++) {
                 const int qs = (o + i) % 11;
                 const float wi = win.w[i];
-                m1 += wi * r0[qs];
-                m2 += wi * r1[qs];
+                m1p += wi * r0[qs];
+                m2p += wi * r1[qs];
                 e11 += wi * r2[qs];
                 e22 += wi * r3[qs];
                 e12 += wi * r4[qs];
             }
             const int gy = blockIdx.y * TH + o;
             {
+                const float m1 = m1p + __builtin_fmaf(cx, dl, cx), m2 = m2p + __builtin_fmaf(cy, dl, cy);
                 const float m1s = m1 * m1, m2s = m2 * m2, m12 = m1 * m2;
-                const float s11 = e11 - m1s, s22 = e22 - m2s, s12 = e12 - m12;
+                const float s11 = (e11 - m1p * m1p) - dl * (cx * (2.f * m1 - cx));
+                const float s22 = (e22 - m2p * m2p) - dl * (cy * (2.f * m2 - cy));
+                const float s12 = (e12 - m1p * m2p) - dl * (cy * m1 + cx * (m2 - cy));
                 const float A = 2.f * m12 + C1, B = 2.f * s12 + C2;
                 const float Cd = m1s + m2s + C1, Dd = s11 + s22 + C2;
                 const float inv_cd = rcp_nr(Cd), inv_dd = rcp_nr(Dd);
@@ -302,9 +340,12 @@ __device__ __forceinline__ void finalize_wave_sums(const float2* __restrict__ pa
         ll += __shfl_xor(ll, o);
     }
 }
-// S, Lv: the 16 wave totals added in wave order
+// S, Lv: the 16 wave totals added in wave order.  No floating-point contraction here: the two
+// kernels this is inlined into otherwise fuse `total` differently (fma(1-lambda, l1, lambda (1-ssim))
+// in k_loss_finalize, fma(lambda, 1-ssim, (1-lambda) l1) in k_ssim_bwd) and their losses differ by an ulp.
 __device__ __forceinline__ void finalize_store(double S, double Lv, float lambda, float inv_n, float* __restrict__ loss,
                                                float* __restrict__ parts) {
+#pragma clang fp contract(off)
     const float ssim = (float)(S * inv_n);
     const float l1 = (float)(Lv * inv_n);
     const float total = (1.0f - lambda) * l1 + lambda * (1.0f - ssim);
@@ -351,7 +392,11 @@ __device__ void loss_finalize_one_wave(const float2* __restrict__ partial, int n
 
 // Backward: the same streamed walk over the three forward maps (G1, G11, G12): horizontal pass
 // from the LDS ring into an 11-row register ring, vertical pass from registers, then the
-// pointwise chain rule.
+// pointwise chain rule.  Where the two images agree G12 = -2 G11, and 2 x blur(G11) + y blur(G12)
+// is a cancellation that leaves the rounding of both blurs where the true gradient is zero
+// (profiles/loss_edges_margins.txt).  So the third plane enters the LDS ring as G12 + 2 G11
+// (PatchRow::store: an exact difference there) and the chain rule uses 2 (x - y) blur(G11) +
+// y blur(G12 + 2 G11): the same sum, without the cancellation after the blur.
 template <int TH>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void k_ssim_bwd(const float* __restrict__ img, const float* __restrict__ gt, int H,
                                                  int W, float lambda, float inv_n, Win win,
@@ -420,7 +465,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void k_
                 const float yv = load_f32(ps[1], vo, so);
                 const float dd = xv - yv;
                 const float sgn = dd > 0.f ? 1.f : (dd < 0.f ? -1.f : 0.f);
-                store_f32(gl * (b1 + 2.f * xv * b11 + yv * b12 + l1k * sgn), ps[2], vo, so);
+                // b12 = blur(G12 + 2 G11): 2 x blur(G11) + y blur(G12) = 2 (x - y) blur(G11) + y b12
+                store_f32(gl * (b1 + 2.f * dd * b11 + yv * b12 + l1k * sgn), ps[2], vo, so);
             }
         }
     }
@@ -465,8 +511,7 @@ int rl_l1_ssim_forward(const float* img, const float* gt, int C, int H, int W, f
         g_err = "rl_l1_ssim_forward: workspace too small";
         return 3;
     }
-    Win win;
-    for (int i = 0; i < 11; i++) win.w[i] = window[i];
+    const Win win = make_win(window);
     const size_t n = (size_t)C * H * W;
     float* g1 = static_cast<float*>(workspace);
     float* g11 = g1 + n;
@@ -495,8 +540,7 @@ int rl_l1_ssim_backward(const float* img, const float* gt, int C, int H, int W, 
         g_err = "rl_l1_ssim_backward: image plane larger than 2^30 bytes";
         return 1;
     }
-    Win win;
-    for (int i = 0; i < 11; i++) win.w[i] = window[i];
+    const Win win = make_win(window);
     const size_t n = (size_t)C * H * W;
     const float* g1 = static_cast<const float*>(workspace);
     const float inv_n = (float)(1.0 / (double)n);
@@ -527,8 +571,7 @@ int rl_l1_ssim_forward_backward(const float* img, const float* gt, int C, int H,
         g_err = "rl_l1_ssim_forward_backward: workspace too small";
         return 3;
     }
-    Win win;
-    for (int i = 0; i < 11; i++) win.w[i] = window[i];
+    const Win win = make_win(window);
     const size_t n = (size_t)C * H * W;
     float* g1 = static_cast<float*>(workspace);
     float2* partial = reinterpret_cast<float2*>(g1 + 3 * n);

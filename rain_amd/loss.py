@@ -54,15 +54,46 @@ def _ones(device):
     return t
 
 
+def _l1_ssim_args(who, img, gt, exact_dims=False, ws=None, with_ws=False):
+    """The argument check every L1+SSIM entry point shares: float32 img / gt of one [.., C, H, W]
+    shape on one HIP device (and a workspace of rl_workspace_bytes for the backward).  Dtype, shape
+    and workspace size are judged before the device.  Returns C, H, W."""
+    for name, t in (("img", img), ("gt", gt)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise RuntimeError(f"{who}: {name} must be a float32 tensor, got "
+                               f"{t.dtype if isinstance(t, torch.Tensor) else type(t).__name__}")
+    if img.dim() != 3 if exact_dims else img.dim() < 3:
+        raise RuntimeError(f"{who}: img must be a [C,H,W] tensor, got {tuple(img.shape)}")
+    C, H, W = img.shape[-3:]
+    if img.numel() != C * H * W or img.numel() == 0:
+        raise RuntimeError(f"{who}: img must be one non-empty [C,H,W] image, got {tuple(img.shape)}")
+    if gt.shape != img.shape:
+        raise RuntimeError(f"{who}: gt must have img's shape {tuple(img.shape)}, got {tuple(gt.shape)}")
+    if with_ws:
+        from . import _native as N
+
+        need = N.loss_lib().rl_workspace_bytes(C, H, W)
+        if not isinstance(ws, torch.Tensor) or not ws.is_contiguous() or ws.numel() * ws.element_size() < need:
+            raise RuntimeError(f"{who}: ws must be a contiguous workspace of at least {need} bytes "
+                               f"(l1_ssim_forward's for the same shape)")
+    if img.device.type != "cuda":
+        raise RuntimeError(f"{who}: img must be on a HIP device (no CPU fallback)")
+    if gt.device != img.device:
+        raise RuntimeError(f"{who}: gt must be on img's device {img.device}, got {gt.device}")
+    if with_ws and ws.device != img.device:
+        raise RuntimeError(f"{who}: ws must be on img's device {img.device}, got {ws.device}")
+    return C, H, W
+
+
 def l1_ssim_forward(img, gt, lambda_dssim):
     """Fused forward (include/rain_loss.h).  Returns (loss scalar, parts [3], workspace); the
     workspace carries the per-pixel SSIM derivative maps the backward needs."""
     from . import _native as N
 
     L = N.loss_lib()
+    C, H, W = _l1_ssim_args("l1_ssim_forward", img, gt)
     img = img.contiguous()
     gt = gt.contiguous()
-    C, H, W = img.shape[-3:]
     ws = torch.empty((L.rl_workspace_bytes(C, H, W),), dtype=torch.uint8, device=img.device)
     loss = torch.empty((), dtype=torch.float32, device=img.device)
     parts = torch.empty((3,), dtype=torch.float32, device=img.device)
@@ -78,9 +109,9 @@ def l1_ssim_backward(img, gt, lambda_dssim, ws, grad_loss=None):
     from . import _native as N
 
     L = N.loss_lib()
+    C, H, W = _l1_ssim_args("l1_ssim_backward", img, gt, ws=ws, with_ws=True)
     img = img.contiguous()
     gt = gt.contiguous()
-    C, H, W = img.shape[-3:]
     dimg = torch.empty_like(img)
     if grad_loss is None:
         grad_loss = _ones(img.device)
@@ -98,9 +129,9 @@ def l1_ssim_forward_backward(img, gt, lambda_dssim, grad_loss=None):
     from . import _native as N
 
     L = N.loss_lib()
+    C, H, W = _l1_ssim_args("l1_ssim_forward_backward", img, gt)
     img = img.contiguous()
     gt = gt.contiguous()
-    C, H, W = img.shape[-3:]
     ws = torch.empty((L.rl_workspace_bytes(C, H, W),), dtype=torch.uint8, device=img.device)
     loss = torch.empty((), dtype=torch.float32, device=img.device)
     parts = torch.empty((3,), dtype=torch.float32, device=img.device)
@@ -140,8 +171,7 @@ class _FusedL1SSIM(torch.autograd.Function):
 
 def fused_l1_ssim_loss(img, gt, lambda_dssim=0.2):
     """Returns (loss, parts) where parts = [loss, L1, SSIM] (device, no sync)."""
-    if img.dim() != 3 or img.device.type != "cuda":
-        raise RuntimeError("fused_l1_ssim_loss expects a [C,H,W] tensor on a HIP device")
+    _l1_ssim_args("fused_l1_ssim_loss", img, gt, exact_dims=True)
     return _FusedL1SSIM.apply(img, gt, lambda_dssim)
 
 
