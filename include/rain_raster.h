@@ -90,6 +90,41 @@ typedef struct rr_frame {
  * when the workspace is not that registered buffer, rr_backward clears the workspace itself. */
 #define RR_FLAG_WORKSPACE_REGISTERED 16
 
+/* Anti-aliased rendering: opacity compensation for the 2D dilation (upstream 3DGS `antialiasing`,
+ * Mip-Splatting's 2D mip filter, gsplat's rasterize_mode="antialiased").  With (a0, b, c0) the EWA 2D
+ * covariance before the dilation, h = low_pass, a = a0 + h and c = c0 + h:
+ *
+ *     det0 = a0 c0 - b^2     det = a c - b^2     rho = det0 / det
+ *     comp = sqrt(max(0.000025, rho))             (upstream's clamp)
+ *     opacity_eff = opacity * comp                (opacity after the sigmoid in raw mode)
+ *
+ * Every later use of the opacity takes opacity_eff: log2 o and 1 / o, the splat record, the wire
+ * record and the tile culling's bound.  Conic, radius, tile rectangle, depth key, colour and normal are
+ * unchanged, so radii and num_rendered are those of the frame without the flag, num_pairs can only
+ * shrink, and a Gaussian whose opacity_eff is below 1/255 keeps its radius and emits no pair.
+ * Backward, with g_o what the blend backward accumulates for the record's opacity:
+ *
+ *     dL/dopacity = g_o comp                              (then the sigmoid backward in raw mode)
+ *     g_rho  = rho <= 0.000025 ? 0 : g_o opacity / (2 comp)
+ *     dL/da += g_rho (c0 det - det0 c) / det^2
+ *     dL/dc += g_rho (a0 det - det0 a) / det^2
+ *     dL/db += g_rho (-2 b) (det - det0) / det^2          (the total derivative in b)
+ *
+ * added before anything downstream of the 2D covariance is formed (also where the conic terms are
+ * zeroed), so scales, rotations, cov3D, means3D, the fused Adam step, the densification statistics
+ * and the next frame's preprocess see them; dL/dmeans2D is unchanged.  With low_pass == 0 the factor
+ * is exactly 1 and the added terms exactly 0.
+ *
+ * Honoured by rr_forward_geometry, rr_forward and rr_forward_render* (set it on both stages, like the
+ * other flags), by rr_backward, rr_backward_aux, rr_backward_aux_normal and rr_backward_aux_dist with
+ * or without rr_grads.adam (outside raw mode the backward still takes no opacities: it reads
+ * opacity_eff back from the frame's geometry buffer), and by rr_grads.next, whose frame carries its
+ * own flag independent of this frame's.  rr_contributions, rr_render_alpha and
+ * rr_backward_records read the record and need nothing.  Refused with RR_ERR_ARG
+ * before any device work (follow-ups): rr_backward_camera with camera gradients, rr_preprocess_rows,
+ * rr_preprocess_rows_views and rr_gauss_backward_views (the Gaussian-sharded step). */
+#define RR_FLAG_ANTIALIAS 32
+
 /* Camera / per-frame device arrays (reference args of the same names). */
 typedef struct rr_camera {
     const float* background; /* [3] */
@@ -378,7 +413,8 @@ int rr_backward_aux_dist(const rr_frame* f, const rr_camera* cam, const rr_gauss
                          const float* dL_dnormal, const float* dL_dmoments, float dist_near, float dist_far,
                          void* workspace, size_t workspace_bytes, const rr_grads* out, void* stream);
 
-/* out_alpha [H*W] = 1 - T_final of the frame last rendered into image_buffer (f: that frame). */
+/* out_alpha [H*W] = 1 - T_final of the frame last rendered into image_buffer (f: that frame).  A frame
+ * rendered with RR_FLAG_ANTIALIAS needs nothing here: T_final was blended from the compensated opacities. */
 int rr_render_alpha(const rr_frame* f, const void* image_buffer, float* out_alpha, void* stream);
 
 /*
@@ -406,6 +442,8 @@ int rr_render_alpha(const rr_frame* f, const void* image_buffer, float* out_alph
  * No host synchronisation; everything runs on stream.  RR_ERR_ARG before any device work for: a null f
  * or out; out not 16-byte aligned; P < 0, width / height <= 0, num_rendered < 0; with P > 0, null
  * radii / geom_buffer / image_buffer.
+ * RR_FLAG_ANTIALIAS needs nothing here: alpha is recomputed from the splat record, whose opacity is the
+ * compensated one, so the statistics are those of the anti-aliased render.
  */
 typedef struct rr_contrib {
     float sum_w;    /* sum_p w_i(p) */

@@ -35,6 +35,7 @@ RR_FLAG_RAW_PARAMS = 2
 RR_FLAG_FULL_BINNING = 4
 RR_FLAG_AUX_NORMAL = 8
 RR_FLAG_WORKSPACE_REGISTERED = 16
+RR_FLAG_ANTIALIAS = 32  # opacity compensation of the 2D dilation (include/rain_raster.h)
 RR_INCOMPLETE = 4  # rr_forward: stage 1 done, binning buffer too small
 
 

@@ -1,7 +1,7 @@
 """Compaction of a trained model by blend-contribution importance (rain_amd.importance).
 
     python -m rain_amd.compact --ply in.ply --out out.ply --fraction 0.6 [--kind weight_volume]
-        [--num_cams 32 --width 800 --height 800 --radius 4.0]
+        [--num_cams 32 --width 800 --height 800 --radius 4.0] [--antialiasing]
 
 Scores every Gaussian over synthetic Fibonacci-sphere cameras (rain_amd.cameras, as
 rain_amd.render_views; the function API of rain_amd.importance takes any camera list), removes the
@@ -32,6 +32,8 @@ def main(argv=None):
     ap.add_argument("--height", type=int, default=800)
     ap.add_argument("--radius", type=float, default=4.0)
     ap.add_argument("--white_background", action="store_true")
+    ap.add_argument("--antialiasing", action="store_true",
+                    help="score the anti-aliased render (PipelineParams.antialiasing)")
     a = ap.parse_args(argv)
     if (a.fraction is None) == (a.threshold is None):
         ap.error("give exactly one of --fraction / --threshold")
@@ -42,7 +44,7 @@ def main(argv=None):
     bg = torch.tensor([1.0, 1.0, 1.0] if a.white_background else [0.0, 0.0, 0.0], device=dev)
     cams = [c.to(dev) for c in fibonacci_cameras(a.num_cams, a.width, a.height, radius=a.radius)]
     before = g.get_xyz.shape[0]
-    stats = importance.accumulate_contributions(g, cams, PipelineParams(), bg)
+    stats = importance.accumulate_contributions(g, cams, PipelineParams(antialiasing=a.antialiasing), bg)
     scores = importance.importance_scores(stats, g, kind=a.kind)
     g.prune_by_importance(scores, fraction=a.fraction, threshold=a.threshold)
     g.save_ply(a.out)

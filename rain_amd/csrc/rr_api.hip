@@ -290,6 +290,7 @@ PreArgs pre_args(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g)
     a.view = cam->viewmatrix; a.proj = cam->projmatrix; a.campos = cam->campos;
     a.cull = (f->flags & RR_FLAG_NO_TILE_CULLING) ? 0 : 1;
     a.raw = (f->flags & RR_FLAG_RAW_PARAMS) ? 1 : 0;
+    a.antialias = (f->flags & RR_FLAG_ANTIALIAS) ? 1 : 0;
     a.shs_rest = g->shs_rest;
     return a;
 }
@@ -301,6 +302,7 @@ GaussBwdArgs gauss_bwd_args(const rr_frame* f, const rr_gaussians* g, const rr_g
     a.scale_modifier = f->scale_modifier;
     a.means3D = g->means3D; a.shs = g->shs; a.scales = g->scales; a.rotations = g->rotations;
     a.raw = (f->flags & RR_FLAG_RAW_PARAMS) ? 1 : 0; a.opacities = g->opacities; a.shs_rest = g->shs_rest;
+    a.antialias = (f->flags & RR_FLAG_ANTIALIAS) ? 1 : 0;
     a.grad_accum = out->grad_accum; a.denom = out->denom; a.max_radii2D = out->max_radii2D;
     a.use_adam = out->adam ? 1 : 0;
     if (out->adam) a.adam = *out->adam;  // by value: the kernel must not dereference host memory
@@ -829,6 +831,8 @@ int backward_impl(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g
     if (pg.dL_dmoments && !dist_range_ok(pg.dist_near, pg.dist_far))
         return fail(RR_ERR_ARG, "dist_near / dist_far must be 0 < near < far, or both 0 (metric depth)");
     const int P = f->P, W = f->width, H = f->height, L = num_rendered;
+    if (cg && (f->flags & RR_FLAG_ANTIALIAS))
+        return fail(RR_ERR_ARG, "RR_FLAG_ANTIALIAS: camera gradients of an anti-aliased frame are not supported yet");
     if (cg) {  // camera gradients (rr_backward_camera): every refusal before any device work
         if (!cg->dL_dviewmatrix || !cg->dL_dprojmatrix || !cg->dL_dcampos)
             return fail(RR_ERR_ARG, "rr_camera_grads: null gradient output");
@@ -907,6 +911,7 @@ int backward_impl(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g
         a.dL_dmeans3D = out->dL_dmeans3D; a.dL_dcov3D = out->dL_dcov3D; a.dL_dsh = f->M > 0 ? out->dL_dsh : nullptr;
         a.dL_dscales = out->dL_dscales; a.dL_drot = out->dL_drotations;
         a.dL_dsh_rest = out->dL_dsh_rest;
+        if (a.antialias) a.splats = carve_geom(const_cast<void*>(geom_buffer), P).splats;
         if (nx) {
             const Geom ng = carve_geom(nx->geom_buffer, P);
             PreArgs n = pre_args(nx->frame, nx->cam, g);
@@ -973,6 +978,8 @@ int rr_preprocess_rows(const rr_frame* f, const rr_camera* cam, const rr_gaussia
                        void* splats, void* tiles, void* depth_keys, void* block_sums, void* block_wide, void* stream) {
     int rc = validate(f, cam, g, true);
     if (rc) return rc;
+    if (f->flags & RR_FLAG_ANTIALIAS)
+        return fail(RR_ERR_ARG, "RR_FLAG_ANTIALIAS: row blocks (the sharded step) are not supported yet");
     if (n_rows < f->P || (n_rows % 256) != 0) return fail(RR_ERR_ARG, "n_rows must be >= P and a multiple of 256");
     if (n_rows == 0) return RR_OK;
     if (!radii || !splats || !tiles || !depth_keys || !block_sums || !block_wide)
@@ -994,6 +1001,8 @@ int rr_preprocess_rows_views(const rr_frame* f, const rr_view* views, int num_vi
                              int n_rows, void* out, size_t view_stride, const size_t field_offsets[6], int wire,
                              void* stream) {
     if (!f || !views || !g || !field_offsets) return fail(RR_ERR_ARG, "null argument");
+    if (f->flags & RR_FLAG_ANTIALIAS)
+        return fail(RR_ERR_ARG, "RR_FLAG_ANTIALIAS: row blocks (the sharded step) are not supported yet");
     if (num_views < 1 || num_views > RR_MAX_VIEWS) return fail(RR_ERR_ARG, "1 <= num_views <= RR_MAX_VIEWS");
     if (n_rows < f->P || (n_rows % 256) != 0) return fail(RR_ERR_ARG, "n_rows must be >= P and a multiple of 256");
     if (f->flags & RR_FLAG_AUX_NORMAL) return fail(RR_ERR_ARG, "row blocks carry no aux normals");
@@ -1110,6 +1119,8 @@ int rr_gauss_backward_views(const rr_frame* f, const rr_view* views, int num_vie
                             const float* records, int record_rows, float grad_scale, const rr_grads* out,
                             void* stream) {
     if (!f || !views || !g || !out) return fail(RR_ERR_ARG, "null argument");
+    if (f->flags & RR_FLAG_ANTIALIAS)
+        return fail(RR_ERR_ARG, "RR_FLAG_ANTIALIAS: the sharded backward is not supported yet");
     if (num_views < 1 || num_views > RR_MAX_VIEWS) return fail(RR_ERR_ARG, "1 <= num_views <= RR_MAX_VIEWS");
     const int P = f->P;
     if (P < 0 || record_rows < P) return fail(RR_ERR_ARG, "bad P / record_rows");

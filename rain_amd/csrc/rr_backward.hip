@@ -242,7 +242,10 @@ __device__ __forceinline__ ViewCam view_cam(const GaussBwdArgs& a) {
 // the forward, so it reaches the rotation only, and joins dL/dq before the raw-mode normalisation.
 // CAM (k_gauss_bwd_cam): this Gaussian's terms of the camera gradients go to cam_out (CamPartials above;
 // left untouched, i.e. zero, for a Gaussian with radius <= 0).
-template <int DEG, bool PACKED, int AUX = 0, bool CAM = false>
+// AA (k_gauss_bwd_aa): built with the anti-aliasing switch.  With a.antialias the record's opacity was
+// o * comp (aa_comp, rr_kernels.hpp): slot 5 is dL/d(o comp), so dL/dopacity = slot 5 * comp and the
+// factor's own gradient joins dL/d(cov2D) before anything downstream of it is formed.
+template <int DEG, bool PACKED, int AUX = 0, bool CAM = false, bool AA = false>
 __device__ __forceinline__ void gauss_bwd_one(const GaussBwdArgs& a, const ViewCam& c, int idx, const GaccRec& rec,
                                               const float* coef, float* gsh, bool acc_sh, SmallGrads& sg,
                                               CamPartials* cam_out = nullptr) {
@@ -319,7 +322,11 @@ __device__ __forceinline__ void gauss_bwd_one(const GaussBwdArgs& a, const ViewC
         dcol[1] = gb.w;
         dcol[2] = g8;
     }
-    if (a.raw) {  // sigmoid backward (torch: grad * (1 - y) * y)
+    bool aa = false;
+    if constexpr (AA) aa = a.antialias != 0;
+    if (aa) {
+        // dL/dopacity waits for the factor (below)
+    } else if (a.raw) {  // sigmoid backward (torch: grad * (1 - y) * y)
         const float o = act_opacity(a.opacities[idx]);
         emit_op(gb.y * (1.0f - o) * o);
     } else {
@@ -355,6 +362,12 @@ __device__ __forceinline__ void gauss_bwd_one(const GaussBwdArgs& a, const ViewC
     const float y_grad_mul = pr.tytz < -pr.limy || pr.tytz > pr.limy ? 0.f : 1.f;
     float ca, cb, cc;
     ewa_cov2d(pr, cov, ca, cb, cc);
+    [[maybe_unused]] float ca0 = 0.f, cc0 = 0.f, det0 = 0.f;
+    if constexpr (AA) {  // the preprocess's det0, by its own expression
+        ca0 = ca;
+        cc0 = cc;
+        det0 = ca * cc - cb * cb;
+    }
     ca += c.low_pass;
     cc += c.low_pass;
     const float denom = ca * cc - cb * cb;
@@ -362,10 +375,36 @@ __device__ __forceinline__ void gauss_bwd_one(const GaussBwdArgs& a, const ViewC
     const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
     const float(&T)[2][3] = pr.A;
     float dc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (denom2inv != 0.f) {
-        dL_da = denom2inv * (-cc * cc * dcx + 2 * cb * cc * dcy + (denom - ca * cc) * dcz);
-        dL_dc = denom2inv * (-ca * ca * dcz + 2 * ca * cb * dcy + (denom - ca * cc) * dcx);
-        dL_db = denom2inv * 2 * (cb * cc * dcx - (denom + 2 * cb * cb) * dcy + ca * cb * dcz);
+    [[maybe_unused]] float aa_da = 0.f, aa_db = 0.f, aa_dc = 0.f;
+    if constexpr (AA) {
+        if (aa) {
+            float rho;
+            const float comp = aa_comp(det0, denom, rho);
+            // outside raw mode the opacity comes back from the record (o comp; comp >= 0.005)
+            const float o = a.raw ? act_opacity(a.opacities[idx]) : a.splats[idx].b.w / comp;
+            const float g_o = gb.y;  // dL/d(o comp)
+            emit_op(a.raw ? g_o * comp * (1.0f - o) * o : g_o * comp);
+            // d comp / d rho = 1 / (2 comp) above the clamp; rho = det0 / det with a = a0 + h, c = c0 + h
+            const float g_rho = rho <= kAaRhoMin ? 0.f : g_o * o / (2.0f * comp);
+            // d rho / d a0 = (c0 det - det0 c) / det^2 and so on, with the differences expanded in h:
+            // c0 det - det0 c = h (c0 c + b^2), det - det0 = h (a0 + c) (no cancellation for large splats)
+            const float s = g_rho * c.low_pass / (denom * denom);
+            aa_da = s * (cc0 * cc + cb * cb);
+            aa_dc = s * (ca0 * ca + cb * cb);
+            aa_db = s * (-2.0f * cb) * (ca0 + cc);
+        }
+    }
+    if (AA || denom2inv != 0.f) {
+        if (denom2inv != 0.f) {
+            dL_da = denom2inv * (-cc * cc * dcx + 2 * cb * cc * dcy + (denom - ca * cc) * dcz);
+            dL_dc = denom2inv * (-ca * ca * dcz + 2 * ca * cb * dcy + (denom - ca * cc) * dcx);
+            dL_db = denom2inv * 2 * (cb * cc * dcx - (denom + 2 * cb * cb) * dcy + ca * cb * dcz);
+        }
+        if constexpr (AA) {  // added even where denom2inv == 0 zeroes the conic terms
+            dL_da += aa_da;
+            dL_dc += aa_dc;
+            dL_db += aa_db;
+        }
         dc[0] = (T[0][0] * T[0][0] * dL_da + T[0][0] * T[1][0] * dL_db + T[1][0] * T[1][0] * dL_dc);
         dc[3] = (T[0][1] * T[0][1] * dL_da + T[0][1] * T[1][1] * dL_db + T[1][1] * T[1][1] * dL_dc);
         dc[5] = (T[0][2] * T[0][2] * dL_da + T[0][2] * T[1][2] * dL_db + T[1][2] * T[1][2] * dL_dc);
@@ -586,7 +625,7 @@ struct GaussBwdViewsArgs;
 // blockIdx.x of cam_partials ([workgroups][kCamRow]; entries 27..31 are written as zeros) through
 // s_cam, an LDS array of (KGB / 64) x kCamStride floats of its own.
 constexpr int kCamStride = 28;
-template <int DEG, bool MULTI, int KGB, int AUX = 0, bool CAM = false>
+template <int DEG, bool MULTI, int KGB, int AUX = 0, bool CAM = false, bool AA = false>
 __device__ __forceinline__ void gauss_bwd_block(const GaussBwdArgs& a, const GaussBwdViewsArgs* va, float* s_sh,
                                                 float* s_gr, float* s_cam = nullptr, float* cam_partials = nullptr);
 
@@ -610,6 +649,14 @@ template <int DEG>
 __global__ __launch_bounds__(kGB1) void k_gauss_bwd_normal(GaussBwdArgs a) {
     __shared__ float s_sh[kGB1 * kShStride];
     gauss_bwd_block<DEG, false, kGB1, 2>(a, nullptr, s_sh, s_sh);
+}
+
+// RR_FLAG_ANTIALIAS on this frame or on the next one (rr_next_frame): the three kernels above built with
+// the switch (AUX 0 plain, 1 depth, 2 normal), so that their own instances stay as they are.
+template <int DEG, int AUX>
+__global__ __launch_bounds__(kGB1) void k_gauss_bwd_aa(GaussBwdArgs a) {
+    __shared__ float s_sh[kGB1 * kShStride];
+    gauss_bwd_block<DEG, false, kGB1, AUX, false, true>(a, nullptr, s_sh, s_sh);
 }
 
 // The camera-gradient variant (launch_gauss_bwd_cam): the depth / alpha kernel (slot 9 is zero when
@@ -684,10 +731,11 @@ __global__ __launch_bounds__(kGB) void k_gauss_bwd_views(GaussBwdViewsArgs va) {
     gauss_bwd_block<DEG, true, kGB>(va.g, &va, s_sh, s_gr);
 }
 
-template <int DEG, bool MULTI, int KGB, int AUX, bool CAM>
+template <int DEG, bool MULTI, int KGB, int AUX, bool CAM, bool AA>
 __device__ __forceinline__ void gauss_bwd_block(const GaussBwdArgs& a, const GaussBwdViewsArgs* va, float* s_sh,
                                                 float* s_gr, float* s_cam, float* cam_partials) {
     static_assert(!(CAM && MULTI), "camera gradients: single view only");
+    static_assert(!(AA && (CAM || MULTI)), "anti-aliasing: the single-view plain / depth / normal kernels only");
     const int t = threadIdx.x, lane = t & 63;
     const int i0 = blockIdx.x * KGB;
     const int nvalid = min(KGB, a.P - i0);
@@ -757,7 +805,7 @@ __device__ __forceinline__ void gauss_bwd_block(const GaussBwdArgs& a, const Gau
         float* row = stage ? s_sh + t * kShStride : nullptr;
         if (!MULTI) {
             const GaccRec rec{a.gacc + (size_t)idx * GACC_STRIDE, a.radii[idx], nullptr};
-            gauss_bwd_one<DEG, false, AUX, CAM>(a, view_cam(a), idx, rec, row, row, false, sg, CAM ? &cp : nullptr);
+            gauss_bwd_one<DEG, false, AUX, CAM, AA>(a, view_cam(a), idx, rec, row, row, false, sg, CAM ? &cp : nullptr);
         } else {
             float* grow = stage ? s_gr + t * kShStride : nullptr;
             // each view's 40-B record is loaded while the previous view is processed (one record
@@ -958,10 +1006,10 @@ __device__ __forceinline__ void gauss_bwd_block(const GaussBwdArgs& a, const Gau
                 const v3 p_view = xform_point_4x3(p, nx.view);  // in_frustum (auxiliary.h:128-153)
                 if (p_view.z > 0.2f) {
                     const float* row = s_sh + t * kShStride;
-                    c = preprocess_finish<DEG, false>(nx, idx, p, p_view,
-                                                      make_float4(upd.v[7], upd.v[8], upd.v[9], upd.v[10]),
-                                                      mk(upd.v[4], upd.v[5], upd.v[6]), upd.v[3],
-                                                      mk(row[0], row[1], row[2]), row + 3, wide);
+                    c = preprocess_finish<DEG, false, AA>(nx, idx, p, p_view,
+                                                          make_float4(upd.v[7], upd.v[8], upd.v[9], upd.v[10]),
+                                                          mk(upd.v[4], upd.v[5], upd.v[6]), upd.v[3],
+                                                          mk(row[0], row[1], row[2]), row + 3, wide);
                 }
             }
             if constexpr (KGB == 256) {
@@ -1051,6 +1099,12 @@ static const GaussBwdKernel kGaussBwdKernels[3][4] = {
     {k_gauss_bwd_depth<0>, k_gauss_bwd_depth<1>, k_gauss_bwd_depth<2>, k_gauss_bwd_depth<3>},
     {k_gauss_bwd_normal<0>, k_gauss_bwd_normal<1>, k_gauss_bwd_normal<2>, k_gauss_bwd_normal<3>},
 };
+// the same rows with the anti-aliasing switch
+static const GaussBwdKernel kGaussBwdKernelsAa[3][4] = {
+    {k_gauss_bwd_aa<0, 0>, k_gauss_bwd_aa<1, 0>, k_gauss_bwd_aa<2, 0>, k_gauss_bwd_aa<3, 0>},
+    {k_gauss_bwd_aa<0, 1>, k_gauss_bwd_aa<1, 1>, k_gauss_bwd_aa<2, 1>, k_gauss_bwd_aa<3, 1>},
+    {k_gauss_bwd_aa<0, 2>, k_gauss_bwd_aa<1, 2>, k_gauss_bwd_aa<2, 2>, k_gauss_bwd_aa<3, 2>},
+};
 static int sh_degree_of(const GaussBwdArgs& a) {
     const int d = a.shs ? a.D : 0;
     return d >= 0 && d < 3 ? d : 3;
@@ -1065,7 +1119,8 @@ void launch_gauss_bwd(const GaussBwdArgs& a, GaussBwdMode mode, hipStream_t st) 
     }
     // a.M <= 16 is validated by the API: the LDS row holds at most 16 coefficients
     const int nb = (a.P + kGB1 - 1) / kGB1;
-    kGaussBwdKernels[mode][sh_degree_of(a)]<<<nb, kGB1, 0, st>>>(a);
+    const bool aa = a.antialias || (a.has_next && a.next.antialias);
+    (aa ? kGaussBwdKernelsAa : kGaussBwdKernels)[mode][sh_degree_of(a)]<<<nb, kGB1, 0, st>>>(a);
 }
 
 int cam_grad_rows(int P) { return P > 0 ? (P + kGB1 - 1) / kGB1 : 1; }

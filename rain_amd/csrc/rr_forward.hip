@@ -20,7 +20,7 @@ namespace rr {
 
 // No global atomics here: per-Gaussian counts go to tiles[idx] = {pairs, rect area} (the rect-area
 // sum is the reference's num_rendered).  The arithmetic is rr_preprocess.hpp's preprocess_finish.
-template <int DEG>
+template <int DEG, bool AA>
 __device__ __forceinline__ uint2 preprocess_one(const PreArgs& a, int idx, bool& wide) {
     preprocess_clear(a, idx);
     const v3 p = load3(a.means3D + 3 * (size_t)idx);
@@ -44,18 +44,18 @@ __device__ __forceinline__ uint2 preprocess_one(const PreArgs& a, int idx, bool&
     const float* dc = a.raw ? a.shs + 3 * (size_t)idx : a.shs + (size_t)idx * a.M * 3;
     const v3 c0 = load3(a.colors_precomp ? a.colors_precomp + 3 * (size_t)idx : dc);
     const float* rest = a.raw ? a.shs_rest + (size_t)idx * (a.M - 1) * 3 : dc + 3;
-    return preprocess_finish<DEG, true>(a, idx, p, p_view, q, sc, o_in, c0, rest, wide);
+    return preprocess_finish<DEG, true, AA>(a, idx, p, p_view, q, sc, o_in, c0, rest, wide);
 }
 
 // The block's sums of {pairs, rect tiles} go to a.block_sums[blockIdx.x] (plain stores; a single
 // contended 64-bit atomic per block measured +37 us on 1M Gaussians).
-template <int DEG>
+template <int DEG, bool AA = false>
 __device__ __forceinline__ void preprocess_block(const PreArgs& a) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     bool wide = false;
     uint2 c = make_uint2(0u, 0u);
     if (idx < a.P) {
-        c = preprocess_one<DEG>(a, idx, wide);
+        c = preprocess_one<DEG, AA>(a, idx, wide);
     } else if (idx < a.n_out) {  // padding row of a row block: culled
         preprocess_clear(a, idx);
     }
@@ -72,6 +72,13 @@ __device__ __forceinline__ void preprocess_block(const PreArgs& a) {
 template <int DEG>
 __global__ __launch_bounds__(256, RR_PRE_OCC) void k_preprocess(PreArgs a) {
     preprocess_block<DEG>(a);
+}
+
+// RR_FLAG_ANTIALIAS: the same kernel built with the switch (rr_preprocess.hpp), so that the instances
+// above stay as they are.
+template <int DEG>
+__global__ __launch_bounds__(256, RR_PRE_OCC) void k_preprocess_aa(PreArgs a) {
+    preprocess_block<DEG, true>(a);
 }
 
 template <int DEG>
@@ -751,6 +758,15 @@ void launch_preprocess(const PreArgs& a, hipStream_t st) {
     const int rows = a.n_out > a.P ? a.n_out : a.P;
     if (rows == 0) return;
     const int nb = blocks_for(rows);
+    if (a.antialias) {
+        switch (a.colors_precomp ? 0 : a.D) {
+            case 0: k_preprocess_aa<0><<<nb, 256, 0, st>>>(a); break;
+            case 1: k_preprocess_aa<1><<<nb, 256, 0, st>>>(a); break;
+            case 2: k_preprocess_aa<2><<<nb, 256, 0, st>>>(a); break;
+            default: k_preprocess_aa<3><<<nb, 256, 0, st>>>(a); break;
+        }
+        return;
+    }
     // (staging the SH coefficients through LDS was measured slower: 1.68 vs 1.66 ms per step)
     switch (a.colors_precomp ? 0 : a.D) {
         case 0: k_preprocess<0><<<nb, 256, 0, st>>>(a); break;

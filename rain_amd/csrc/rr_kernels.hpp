@@ -61,7 +61,19 @@ struct PreArgs {
                                  // no pairs, the largest depth key) — the padding rows of a row block
     float* wire;                 // optional (the sharded step's send chunks): per row the 10-float
                                  // wire record (splat_to_wire) instead of splats[] and depth_keys[]
+    int antialias;               // RR_FLAG_ANTIALIAS: opacity times aa_comp() (read by the kernels built
+                                 // with the switch only: k_preprocess_aa, k_gauss_bwd_aa)
 };
+
+// RR_FLAG_ANTIALIAS (include/rain_raster.h): the opacity compensation of the 2D dilation.  det0 is the
+// determinant of the EWA covariance before low_pass joins its diagonal, det the one after;
+// rho = det0 / det, and the factor is sqrt(max(0.000025, rho)) (upstream's clamp).  One function for
+// the preprocess and the per-Gaussian backward, so both form the same factor from the same inputs.
+constexpr float kAaRhoMin = 0.000025f;
+__device__ __forceinline__ float aa_comp(float det0, float det, float& rho) {
+    rho = det0 / det;
+    return sqrtf(fmaxf(kAaRhoMin, rho));
+}
 
 // The sharded step's wire record of a splat: the 10 floats Splat holds that cannot be recomputed
 // (x, y, qa, qb, qc, depth, o, r, g, b); log2 o, 1/o and the depth key are rebuilt by the
@@ -192,12 +204,17 @@ struct GaussBwdArgs {
     // camera, frame values and output arrays (geometry buffer, radii); has_next says whether valid
     PreArgs next;
     int has_next;
+    int antialias;  // RR_FLAG_ANTIALIAS of this frame (launch_gauss_bwd then takes the k_gauss_bwd_aa row)
+    // with antialias outside raw mode (the backward gets no opacities there): the frame's records, whose
+    // opacity is o comp
+    const Splat* splats;
 };
 // The per-Gaussian backward in `mode` (rr_bwd_plan.hpp; not kGaussBwdCam, which is launch_gauss_bwd_cam):
 // kGaussBwdDepth — the accumulators come from an aux blend backward; slot 9, dL/d(view depth), is read
 // and chained into dL/dmeans3D through the view matrix's z row.  kGaussBwdNormal — slot 9 as above, and
 // slots 10..12, dL/d(view-space unit normal), are chained into dL/drotations (a.scales / a.rotations
-// required).
+// required).  A frame with a.antialias, or a next frame with a.next.antialias, runs the mode's
+// k_gauss_bwd_aa kernel (the row of the same mode built with the switch).
 void launch_gauss_bwd(const GaussBwdArgs& a, GaussBwdMode mode, hipStream_t st);
 // camera (rr_backward_camera): the depth variant plus the gradients of the camera arrays.  Every
 // workgroup leaves the sums of its Gaussians' 27 camera terms in its row of partials

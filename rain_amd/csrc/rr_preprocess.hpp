@@ -17,7 +17,8 @@ __device__ __forceinline__ void preprocess_clear(const PreArgs& a, int idx) {
 // Everything after the frustum test, on inputs already in registers: p (mean), p_view, q / sc
 // (raw in raw mode), o_in (opacity or its logit), c0 (SH DC or precomputed colour) and `rest`
 // (SH coefficients 1.., read as VEC_REST ? 16-B loads of global memory : scalars, e.g. an LDS row).
-template <int DEG, bool VEC_REST>
+// AA: built with the anti-aliasing switch (a.antialias is read by these instances only).
+template <int DEG, bool VEC_REST, bool AA = false>
 __device__ __forceinline__ uint2 preprocess_finish(const PreArgs& a, int idx, v3 p, v3 p_view, float4 q, v3 sc,
                                                    float o_in, v3 c0, const float* rest, bool& wide) {
     const float4 p_hom = xform_point_4x4(p, a.proj);
@@ -39,6 +40,8 @@ __device__ __forceinline__ uint2 preprocess_finish(const PreArgs& a, int idx, v3
     const Proj2D pr = ewa_setup(p, a.focal_x, a.focal_y, a.tanfovx, a.tanfovy, a.view);
     float ca, cb, cc;
     ewa_cov2d(pr, cov, ca, cb, cc);
+    [[maybe_unused]] float det0 = 0.f;
+    if constexpr (AA) det0 = ca * cc - cb * cb;
     ca += a.low_pass;
     cc += a.low_pass;
 
@@ -78,7 +81,13 @@ __device__ __forceinline__ uint2 preprocess_finish(const PreArgs& a, int idx, v3
         const v3 c = sh_eval<DEG>(dir, c0, rr);
         rgb = make_float4(fmaxf(c.x, 0.f), fmaxf(c.y, 0.f), fmaxf(c.z, 0.f), 0.f);
     }
-    const float opacity = a.raw ? act_opacity(o_in) : o_in;
+    float opacity = a.raw ? act_opacity(o_in) : o_in;
+    if constexpr (AA) {  // every later use (log2 o, 1/o, the record, the wire record, cull_qmax) takes o * comp
+        if (a.antialias) {
+            float rho;
+            opacity *= aa_comp(det0, det, rho);
+        }
+    }
     float log2o, inv_o;
     splat_derived(opacity, log2o, inv_o);
     Splat s;

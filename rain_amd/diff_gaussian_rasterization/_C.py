@@ -14,6 +14,8 @@ takes a gradient of the aux normal map of ``rasterize_gaussians_aux`` as well (r
 ``rasterize_gaussians_backward_dist`` takes their gradient (rr_forward_render_dist, rr_backward_aux_dist);
 ``rasterize_gaussians_backward_camera`` is ``rasterize_gaussians_backward_depth`` that also returns the
 gradients of the camera arrays (viewmatrix, projmatrix, campos; rr_backward_camera).
+``antialiased()`` makes the calls inside its block render and differentiate anti-aliased frames
+(RR_FLAG_ANTIALIAS: the opacity compensation of the 2D dilation).
 
 Differences that are deliberate and invisible to callers: scratch buffers are sized by the C
 ABI's *_bytes() queries instead of grown through std::function callbacks; outputs the kernels
@@ -23,8 +25,10 @@ reference uses the current device and the legacy default stream).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
+import threading
 
 import torch
 
@@ -67,8 +71,29 @@ def _require_device(means3D):
     return means3D.device
 
 
+# Anti-aliased rendering (include/rain_raster.h RR_FLAG_ANTIALIAS).  The functions below keep the
+# reference's argument lists, so the switch travels beside them: inside `with antialiased():` every
+# rasterize_gaussians* call of this thread, forward or backward, builds its frame with the flag.  A
+# frame's backward must run under the value its forward ran under (the autograd classes record it).
+_SWITCH = threading.local()
+
+
+def antialiasing_on() -> bool:
+    return bool(getattr(_SWITCH, "antialiasing", False))
+
+
+@contextlib.contextmanager
+def antialiased(on=True):
+    prev = antialiasing_on()
+    _SWITCH.antialiasing = bool(on)
+    try:
+        yield
+    finally:
+        _SWITCH.antialiasing = prev
+
+
 def _frame(P, degree, M, W, H, tan_fovx, tan_fovy, scale_modifier, low_pass, prefiltered, debug):
-    flags = frame_flags()
+    flags = frame_flags() | (N.RR_FLAG_ANTIALIAS if antialiasing_on() else 0)
     return N.RRFrame(int(P), int(degree), int(M), int(W), int(H), float(tan_fovx), float(tan_fovy),
                      float(scale_modifier), float(low_pass), int(bool(prefiltered)), int(bool(debug)), flags)
 
@@ -201,7 +226,11 @@ def rasterize_gaussians_backward_camera(background, means3D, radii, colors, scal
     `viewmatrix`, `projmatrix` and `campos` as three independent inputs, in their memory layout.  The
     view matrix is reached through the EWA Jacobian, its 3x3 block and the view depth of the depth map;
     the projection through means2D (its z row gets 0); campos through the SH view direction (0 with
-    precomputed colours).  The depth and alpha gradients may both be empty (a colour-only loss)."""
+    precomputed colours).  The depth and alpha gradients may both be empty (a colour-only loss).
+    Raises inside antialiased(): camera gradients of an anti-aliased frame are a follow-up."""
+    if antialiasing_on():
+        raise RuntimeError("rasterize_gaussians_backward_camera: camera gradients do not combine with "
+                           "antialiasing yet (RR_FLAG_ANTIALIAS)")
     return _backward("rasterize_gaussians_backward_camera", background, means3D, radii, colors, scales,
                      rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy,
                      dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, low_pass,
@@ -281,7 +310,8 @@ def _backward(label, background, means3D, radii, colors, scales, rotations, scal
         view=_dev_f32(viewmatrix, device, "viewmatrix"), proj=_dev_f32(projmatrix, device, "projmatrix"),
         sh=_dev_f32(sh, device, "sh"), campos=_dev_f32(campos, device, "campos"), radii=radii.contiguous())
     dpix, ddepth, dalpha, dnormal, dmoments = (_dev_f32(t, device, name) for name, t, _ in maps)
-    # opacities are not needed by the backward (the reference does not pass them either)
+    # opacities are not needed by the backward (the reference does not pass them either; an anti-aliased
+    # frame's backward reads the compensated opacity back from the geometry buffer)
     frame = _frame(P, degree, M, W, H, tan_fovx, tan_fovy, scale_modifier, low_pass, False, debug)
     if nrm:  # the forward was rasterize_gaussians_aux
         frame.flags |= N.RR_FLAG_AUX_NORMAL

@@ -10,6 +10,7 @@ Gaussian-Splatting licence, LICENSE.md there) — ``rasterize_gaussians`` (:10-3
 9-79) runs against it unchanged.  The code is organised differently: argument packing and the
 debug snapshot are shared helpers.
 """
+import contextlib
 from typing import NamedTuple
 
 import torch
@@ -20,6 +21,8 @@ from . import _C
 _MSG_COLOR = 'Please provide excatly one of either SHs or precomputed colors!'  # reference text, typo included
 _MSG_COV = 'Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!'
 _MSG_DIST = 'forward_distortion needs 0 < dist_near < dist_far, or both 0 (metric depth)'
+_MSG_AA_CAMERA = ('forward_camera does not combine with antialiasing yet (follow-up: camera-pose gradients of an '
+                  'anti-aliased frame, RR_FLAG_ANTIALIAS)')
 _MSG_NORMAL = 'render_depth_normal needs the scale/rotation pair (normals come from the scale axes)'
 
 
@@ -37,6 +40,21 @@ class GaussianRasterizationSettings(NamedTuple):
     prefiltered: bool
     debug: bool
     low_pass: float
+
+
+def _antialiased(on):
+    """_C.antialiased(on): the calls inside the block serve anti-aliased frames.  A stand-in `_C` without the
+    switch (a CPU oracle bound in its place) serves plain frames only."""
+    if hasattr(_C, "antialiased"):
+        return _C.antialiased(on)
+    if on:
+        raise RuntimeError("antialiasing needs the rasterizer's own _C (this one has no antialiased() switch)")
+    return contextlib.nullcontext()
+
+
+def _antialiasing_on():
+    fn = getattr(_C, "antialiasing_on", None)
+    return bool(fn is not None and fn())
 
 
 def _host_copy(values):
@@ -85,6 +103,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             "\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
         ctx.raster_settings = s
         ctx.num_rendered = num_rendered
+        ctx.antialiasing = _antialiasing_on()  # the frame's switch (_C.antialiased), for its backward
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning,
                               img)
         return color, radii, depth
@@ -94,9 +113,10 @@ class _RasterizeGaussians(torch.autograd.Function):
         # depth receives no gradient: grad_depth is accepted and dropped (__init__.py:91-120)
         s = ctx.raster_settings
         args = _backward_args(s, ctx.saved_tensors, ctx.num_rendered, grad_out_color)
-        d_means2D, d_colors, d_opacities, d_means3D, d_cov3D, d_sh, d_scales, d_rotations = _invoke(
-            _C.rasterize_gaussians_backward, args, s.debug, "snapshot_bw.dump",
-            "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
+        with _antialiased(ctx.antialiasing):
+            d_means2D, d_colors, d_opacities, d_means3D, d_cov3D, d_sh, d_scales, d_rotations = _invoke(
+                _C.rasterize_gaussians_backward, args, s.debug, "snapshot_bw.dump",
+                "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
         # order of forward()'s inputs; raster_settings gets None
         return d_means3D, d_means2D, d_sh, d_colors, d_opacities, d_scales, d_rotations, d_cov3D, None
 
@@ -123,6 +143,7 @@ def _aux_forward(ctx, inputs, raster_settings, normal=False, dist=None, camera=N
     ctx.raster_settings = s
     ctx.num_rendered = num_rendered
     ctx.dist = dist or ()
+    ctx.antialiasing = _antialiasing_on()  # the frame's switch (_C.antialiased), for its backward
     ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning,
                           img)
     ctx.mark_non_differentiable(radii)
@@ -141,9 +162,10 @@ def _aux_backward(ctx, fn, grads, n_inputs, camera=False):
     grads = _absent_as_empty(*grads)  # "absent" (a NULL pointer in the library)
     args = _backward_args(s, ctx.saved_tensors, ctx.num_rendered, grads[0]) + grads[1:] + ctx.dist
     camera = camera and any(ctx.needs_input_grad[9:12])  # a fixed camera: the plain depth backward
-    d_means2D, d_colors, d_opacities, d_means3D, d_cov3D, d_sh, d_scales, d_rotations, *d_cam = _invoke(
-        _C.rasterize_gaussians_backward_camera if camera else fn, args, s.debug, "snapshot_bw.dump",
-        "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
+    with _antialiased(ctx.antialiasing):
+        d_means2D, d_colors, d_opacities, d_means3D, d_cov3D, d_sh, d_scales, d_rotations, *d_cam = _invoke(
+            _C.rasterize_gaussians_backward_camera if camera else fn, args, s.debug, "snapshot_bw.dump",
+            "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
     # (in the inputs' own shapes: a flat [16] matrix gets a flat gradient)
     d_cam = tuple(g.view(shape) for g, shape in zip(d_cam, ctx.cam_shapes)) if camera else ()
     res = (d_means3D, d_means2D, d_sh, d_colors, d_opacities, d_scales, d_rotations, d_cov3D, None) + d_cam
@@ -249,9 +271,15 @@ def _checked_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp, norma
 
 
 class GaussianRasterizer(nn.Module):
-    def __init__(self, raster_settings):
+    def __init__(self, raster_settings, antialiasing=False):
+        """antialiasing (upstream 3DGS's name; it travels beside the 13 settings fields): every splat's
+        opacity is scaled by sqrt(max(0.000025, det(cov2D) / det(cov2D + low_pass I))), the opacity
+        compensation of the 2D dilation, and the factor's gradient reaches the covariance
+        (include/rain_raster.h RR_FLAG_ANTIALIAS).  Every forward* below and its backward honour it, as do
+        contributions() and render_depth_normal(); forward_camera refuses it."""
         super().__init__()
         self.raster_settings = raster_settings
+        self.antialiasing = bool(antialiasing)
 
     def markVisible(self, positions):
         s = self.raster_settings
@@ -262,8 +290,9 @@ class GaussianRasterizer(nn.Module):
                 cov3D_precomp=None):
         shs, colors_precomp, scales, rotations, cov3D_precomp = _checked_inputs(shs, colors_precomp, scales,
                                                                                 rotations, cov3D_precomp)
-        return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                   cov3D_precomp, self.raster_settings)
+        with _antialiased(self.antialiasing):
+            return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+                                       cov3D_precomp, self.raster_settings)
 
     def forward_depth(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                       cov3D_precomp=None):
@@ -274,8 +303,9 @@ class GaussianRasterizer(nn.Module):
         path's (no mask for the 0.99 alpha clamp, dL/dmeans2D in NDC units)."""
         shs, colors_precomp, scales, rotations, cov3D_precomp = _checked_inputs(shs, colors_precomp, scales,
                                                                                 rotations, cov3D_precomp)
-        return _RasterizeGaussiansDepth.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                              cov3D_precomp, self.raster_settings)
+        with _antialiased(self.antialiasing):
+            return _RasterizeGaussiansDepth.apply(means3D, means2D, shs, colors_precomp, opacities, scales,
+                                                  rotations, cov3D_precomp, self.raster_settings)
 
     def forward_camera(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                        cov3D_precomp=None):
@@ -285,7 +315,10 @@ class GaussianRasterizer(nn.Module):
         layout — to whatever produced those tensors (rain_amd.cameras.CameraPose).  The view matrix is
         reached through the EWA Jacobian, its 3x3 block and the view depth of the depth map; the
         projection through means2D only (its z row gets 0); campos through the SH view direction (0
-        with colors_precomp).  Culling, radii and the depth order are discrete and contribute nothing."""
+        with colors_precomp).  Culling, radii and the depth order are discrete and contribute nothing.
+        A rasterizer built with antialiasing=True raises a ValueError (a follow-up)."""
+        if self.antialiasing:
+            raise ValueError(_MSG_AA_CAMERA)
         shs, colors_precomp, scales, rotations, cov3D_precomp = _checked_inputs(shs, colors_precomp, scales,
                                                                                 rotations, cov3D_precomp)
         s = self.raster_settings
@@ -302,8 +335,9 @@ class GaussianRasterizer(nn.Module):
         scale/rotation pair (cov3D_precomp is refused)."""
         shs, colors_precomp, scales, rotations, cov3D_precomp = _checked_inputs(
             shs, colors_precomp, scales, rotations, cov3D_precomp, normal=True)
-        return _RasterizeGaussiansNormal.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                               cov3D_precomp, self.raster_settings)
+        with _antialiased(self.antialiasing):
+            return _RasterizeGaussiansNormal.apply(means3D, means2D, shs, colors_precomp, opacities, scales,
+                                                   rotations, cov3D_precomp, self.raster_settings)
 
     def forward_distortion(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None,
                            rotations=None, cov3D_precomp=None, dist_near=0.2, dist_far=100.0, normal=False):
@@ -319,8 +353,9 @@ class GaussianRasterizer(nn.Module):
         near, far = float(dist_near), float(dist_far)
         if not ((near == 0.0 and far == 0.0) or (0.0 < near < far < float("inf"))):
             raise Exception(_MSG_DIST)
-        return _RasterizeGaussiansDist.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                             cov3D_precomp, self.raster_settings, near, far, bool(normal))
+        with _antialiased(self.antialiasing):
+            return _RasterizeGaussiansDist.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+                                                 cov3D_precomp, self.raster_settings, near, far, bool(normal))
 
     @torch.no_grad()
     def contributions(self, means3D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
@@ -334,7 +369,8 @@ class GaussianRasterizer(nn.Module):
                                                                         cov3D_precomp)
         s = self.raster_settings
         args = _forward_args(s, means3D, colors_precomp, opacities, scales, rotations, cov3D, shs)
-        num_rendered, color, radii, _depth, geom, binning, img = _C.rasterize_gaussians(*args)
+        with _antialiased(self.antialiasing):
+            num_rendered, color, radii, _depth, geom, binning, img = _C.rasterize_gaussians(*args)
         stats = _C.gaussian_contributions(radii, geom, binning, img, num_rendered, means3D.size(0), s.image_width,
                                           s.image_height, pixel_weight=pixel_weight, out=out)
         return color, radii, stats
@@ -351,7 +387,8 @@ class GaussianRasterizer(nn.Module):
             raise Exception(_MSG_NORMAL)
         shs, colors_precomp, cov3D = _absent_as_empty(shs, colors_precomp, None)
         args = _forward_args(self.raster_settings, means3D, colors_precomp, opacities, scales, rotations, cov3D, shs)
-        out = _C.rasterize_gaussians_aux(*args)
+        with _antialiased(self.antialiasing):
+            out = _C.rasterize_gaussians_aux(*args)
         return out[1], out[2], out[3], out[4]
 
 

@@ -67,7 +67,8 @@ class BinningCache:
 
 
 def forward(model, camera, bg: torch.Tensor, low_pass: float, scale_modifier: float = 1.0,
-            cache: BinningCache | None = None, normal: bool = False, dist: tuple | None = None):
+            cache: BinningCache | None = None, normal: bool = False, dist: tuple | None = None,
+            antialiasing: bool = False):
     """Render `camera` from `model` (a GaussianModel) in raw-parameter mode.
     Returns (color [3,H,W], radii [P] int32, depth [1,H,W], RawFrame).  With `cache` the binning
     buffer is reused (see BinningCache) and must not be needed by an earlier frame's pending
@@ -76,21 +77,24 @@ def forward(model, camera, bg: torch.Tensor, low_pass: float, scale_modifier: fl
     frame always runs its own preprocess (it cannot be the `next_frame` of an earlier backward).
     With `dist` = (dist_near, dist_far) the frame also renders the depth-moment maps of the distortion
     loss (rr_forward_render_dist), left in the RawFrame's `moments` field ([2,H,W]);
-    backward(dL_dmoments=...) differentiates them.  It runs its own preprocess as well."""
+    backward(dL_dmoments=...) differentiates them.  It runs its own preprocess as well.
+    With `antialiasing` the frame carries RR_FLAG_ANTIALIAS (the opacity compensation of the 2D
+    dilation, include/rain_raster.h); its backward reads the flag from the RawFrame."""
     params = (model._xyz, model._features_dc, model._features_rest, model._opacity, model._scaling,
               model._rotation)
     return forward_params(params, model.active_sh_degree, int(camera.image_width), int(camera.image_height),
                           math.tan(camera.FoVx * 0.5), math.tan(camera.FoVy * 0.5), camera.world_view_transform,
                           camera.full_proj_transform, camera.camera_center, bg, low_pass, scale_modifier, cache,
-                          normal, dist)
+                          normal, dist, antialiasing)
 
 
 def forward_params(params, sh_degree: int, W: int, H: int, tanfovx: float, tanfovy: float, viewmatrix, projmatrix,
                    campos, bg: torch.Tensor, low_pass: float, scale_modifier: float = 1.0,
-                   cache: BinningCache | None = None, normal: bool = False, dist: tuple | None = None):
+                   cache: BinningCache | None = None, normal: bool = False, dist: tuple | None = None,
+                   antialiasing: bool = False):
     """forward() on explicit raw parameters (xyz, f_dc, f_rest, opacity, scaling, rotation) — the
     GaussianModel attributes before activation — and camera values as render() puts them in
-    GaussianRasterizationSettings.  `normal`, `dist`: see forward()."""
+    GaussianRasterizationSettings.  `normal`, `dist`, `antialiasing`: see forward()."""
     xyz = params[0]
     dev = xyz.device
     if dev.type != "cuda":
@@ -101,7 +105,8 @@ def forward_params(params, sh_degree: int, W: int, H: int, tanfovx: float, tanfo
     M = 1 + f_rest.shape[1]
     D = int(sh_degree)
     L = N.raster()
-    flags = N.RR_FLAG_RAW_PARAMS | _C.frame_flags() | (N.RR_FLAG_AUX_NORMAL if normal else 0)
+    flags = N.RR_FLAG_RAW_PARAMS | _C.frame_flags() | (N.RR_FLAG_AUX_NORMAL if normal else 0) | \
+        (N.RR_FLAG_ANTIALIAS if antialiasing else 0)
     frame = N.RRFrame(P, D, M, W, H, float(tanfovx), float(tanfovy), float(scale_modifier), float(low_pass), 0, 0,
                       flags)
     keep = (bg.contiguous(), viewmatrix.contiguous(), projmatrix.contiguous(), campos.contiguous())
@@ -209,9 +214,11 @@ class NextFrame:
                                   self.geom.numel())
 
 
-def prepare_next(model, camera, bg: torch.Tensor, low_pass: float, scale_modifier: float = 1.0) -> NextFrame:
+def prepare_next(model, camera, bg: torch.Tensor, low_pass: float, scale_modifier: float = 1.0,
+                 antialiasing: bool = False) -> NextFrame:
     """The next frame's descriptor and output buffers (geometry buffer, radii) for `camera` at the
-    model's current P, M and SH degree."""
+    model's current P, M and SH degree.  `antialiasing` is the next frame's own RR_FLAG_ANTIALIAS,
+    independent of the flag of the frame whose backward runs this preprocess."""
     xyz = model._xyz
     dev = xyz.device
     P = xyz.shape[0]
@@ -220,7 +227,7 @@ def prepare_next(model, camera, bg: torch.Tensor, low_pass: float, scale_modifie
     L = N.raster()
     frame = N.RRFrame(P, int(model.active_sh_degree), M, W, H, math.tan(camera.FoVx * 0.5),
                       math.tan(camera.FoVy * 0.5), float(scale_modifier), float(low_pass), 0, 0,
-                      N.RR_FLAG_RAW_PARAMS | _C.frame_flags())
+                      N.RR_FLAG_RAW_PARAMS | _C.frame_flags() | (N.RR_FLAG_ANTIALIAS if antialiasing else 0))
     keep = (bg.contiguous(), camera.world_view_transform.contiguous(), camera.full_proj_transform.contiguous(),
             camera.camera_center.contiguous())
     cam = N.RRCamera(*[_p(t) for t in keep])
@@ -291,8 +298,12 @@ def backward(st: RawFrame, dL_dpix: torch.Tensor, grads: dict | None, stats: tup
     reaches xyz through the view depth and everything else through alpha_i.
     `cam_grads` = (d_viewmatrix [4,4], d_projmatrix [4,4], d_campos [3]) (contiguous fp32, optional): they
     receive the gradients of the frame's three camera arrays (rr_backward_camera), fully overwritten.
-    Colour, depth and alpha gradients only, and no `adam` / `next_frame`."""
+    Colour, depth and alpha gradients only, and no `adam` / `next_frame`, and not on a frame rendered with
+    antialiasing (a follow-up)."""
     if cam_grads is not None:
+        if st is not None and st.frame.flags & N.RR_FLAG_ANTIALIAS:
+            raise RuntimeError("rain_amd.fused.backward: camera gradients do not combine with antialiasing yet "
+                               "(RR_FLAG_ANTIALIAS)")
         if dL_dnormal is not None or dL_dmoments is not None:
             raise RuntimeError("rain_amd.fused.backward: camera gradients do not combine with dL_dnormal / "
                                "dL_dmoments yet")
@@ -381,7 +392,12 @@ def _raw_forward(ctx, inputs, aux=True, normal=False, dist=None, camera=False):
     """The forward of the five classes below on their 18 common `inputs`: (color, radii, depth), with `aux`
     the accumulated alpha as well (depth then carries gradients), then the aux normal map with `normal`
     (None without it, in a dist frame), then the moment maps with `dist` = (near, far).  `camera`: the three
-    camera arrays are differentiable inputs."""
+    camera arrays are differentiable inputs.  Inside `with _C.antialiased():` (the classes keep their 18
+    inputs, so the switch travels beside them) the frame, and with it its backward, carries RR_FLAG_ANTIALIAS."""
+    antialiasing = _C.antialiasing_on()
+    if camera and antialiasing:
+        raise ValueError("render(pose_grad=True) does not combine with antialiasing yet (follow-up: camera-pose "
+                         "gradients of an anti-aliased frame)")
     (xyz, f_dc, f_rest, opacity, scaling, rotation, _means2D, sh_degree, W, H, tanfovx, tanfovy, viewmatrix,
      projmatrix, campos, bg, low_pass, scale_modifier) = inputs
     if camera:
@@ -390,7 +406,8 @@ def _raw_forward(ctx, inputs, aux=True, normal=False, dist=None, camera=False):
         ctx.cam_shapes = (viewmatrix.shape, projmatrix.shape, campos.shape)
     color, radii, depth, st = forward_params((xyz, f_dc, f_rest, opacity, scaling, rotation), sh_degree, W, H,
                                              tanfovx, tanfovy, viewmatrix, projmatrix, campos, bg, low_pass,
-                                             scale_modifier, normal=normal, dist=dist)
+                                             scale_modifier, normal=normal, dist=dist,
+                                             antialiasing=bool(antialiasing))
     # the parameters as saved tensors (the reference saves its inputs, __init__.py:85-87): autograd's
     # version check then rejects a backward after they were modified in place.  The scratch
     # buffers and camera tensors are saved too, so that autograd frees them after a backward

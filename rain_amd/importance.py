@@ -55,7 +55,7 @@ class ContributionStats:
 def accumulate_contributions(gaussians, views, pipe, background, pixel_weight_fn=None, low_pass=0.3):
     """One render plus one statistics launch per view, all into one buffer.  pixel_weight_fn(view, image)
     -> [H,W] (optional) weights the pixels of sum_gw, e.g. a per-pixel error map or a mask; without it
-    sum_gw is sum_w."""
+    sum_gw is sum_w.  pipe.antialiasing is honoured."""
     P = gaussians.get_xyz.shape[0]
     buf = torch.zeros((P, 4), dtype=torch.float32, device=gaussians.get_xyz.device)
     stats = ContributionStats(buf, 0)
@@ -72,7 +72,9 @@ def accumulate_contributions(gaussians, views, pipe, background, pixel_weight_fn
             viewmatrix=view.world_view_transform, projmatrix=view.full_proj_transform,
             sh_degree=gaussians.active_sh_degree, campos=view.camera_center, prefiltered=False,
             debug=bool(pipe is not None and pipe.debug), low_pass=low_pass)
-        r = GaussianRasterizer(settings)
+        # pipe.antialiasing: the statistics are then those of the anti-aliased render (rr_contributions reads
+        # the splat records, which hold the compensated opacities)
+        r = GaussianRasterizer(settings, antialiasing=bool(getattr(pipe, "antialiasing", False)))
         kw = dict(shs=shs, scales=scales, rotations=rotations, cov3D_precomp=cov3D)
         if pixel_weight_fn is None:
             r.contributions(means3D, opacity, out=buf, **kw)

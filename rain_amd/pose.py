@@ -18,7 +18,11 @@ def refine_pose(camera, pc, pipe, bg, target_image, iters, lr, target_depth=None
     `pc` matches `target_image` [3,H,W]: Adam (`lr`, `iters` steps) on CameraPose's rot_delta and
     trans_delta.  The loss is the mean L1 on colour, plus the mean L1 between depth / alpha and
     `target_depth` [1,H,W] where that is given (pixels with alpha > 0).  Returns (pose, losses): the
-    CameraPose and the loss of every iteration (floats, evaluated before that iteration's step)."""
+    CameraPose and the loss of every iteration (floats, evaluated before that iteration's step).
+    pipe.antialiasing raises a ValueError: camera gradients of an anti-aliased frame are a follow-up."""
+    if bool(getattr(pipe, "antialiasing", False)):
+        raise ValueError("refine_pose does not combine with pipe.antialiasing yet (follow-up: camera-pose gradients "
+                         "of an anti-aliased frame)")
     pose = camera if isinstance(camera, CameraPose) else CameraPose(camera)
     params = [pose.rot_delta, pose.trans_delta]
     opt = torch.optim.Adam(params, lr=lr)

@@ -60,7 +60,7 @@ def render_set(model_path, name, iteration, views, gaussians, pipeline, backgrou
     for idx, view in enumerate(views):
         with torch.no_grad():
             if normals:
-                out = render_depth_normal(view, gaussians, background)
+                out = render_depth_normal(view, gaussians, background, pipe=pipeline)
             else:
                 out = render(view, gaussians, pipeline, background)
         image, depth = out["render"], out["depth"]
@@ -91,13 +91,16 @@ def main(argv=None):
     ap.add_argument("--radius", type=float, default=4.0)
     ap.add_argument("--white_background", action="store_true")
     ap.add_argument("--normals", action="store_true")
+    ap.add_argument("--antialiasing", action="store_true",
+                    help="opacity compensation of the 2D dilation (PipelineParams.antialiasing)")
     a = ap.parse_args(argv)
     dev = torch.device("cuda", torch.cuda.current_device())
     g = GaussianModel(a.sh_degree, device=dev)
     g.load_ply(a.ply)
     bg = torch.tensor([1.0, 1.0, 1.0] if a.white_background else [0.0, 0.0, 0.0], device=dev)
     cams = [c.to(dev) for c in fibonacci_cameras(a.num_cams, a.width, a.height, radius=a.radius)]
-    render_set(a.model_path, "test", a.iteration, cams, g, PipelineParams(), bg, normals=a.normals)
+    render_set(a.model_path, "test", a.iteration, cams, g, PipelineParams(antialiasing=a.antialiasing), bg,
+               normals=a.normals)
 
 
 if __name__ == "__main__":

@@ -66,6 +66,9 @@ class PipelineParams:
     convert_SHs_python: bool = False
     compute_cov3D_python: bool = False
     debug: bool = False
+    # upstream 3DGS's `antialiasing`: opacity compensation of the 2D dilation (Mip-Splatting's 2D mip
+    # filter; include/rain_raster.h RR_FLAG_ANTIALIAS)
+    antialiasing: bool = False
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
@@ -80,9 +83,15 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     `pose_grad` (which implies depth_grad; not with normal_grad / dist_grad yet) makes the camera a
     differentiable input: the gradients of viewpoint_camera.world_view_transform, full_proj_transform
     and camera_center reach whatever produced them (rain_amd.cameras.CameraPose;
-    GaussianRasterizer.forward_camera)."""
+    GaussianRasterizer.forward_camera).  pipe.antialiasing renders anti-aliased (every splat's opacity times
+    sqrt(det cov2D / det(cov2D + low_pass I)), with the factor's gradient; RR_FLAG_ANTIALIAS) on either route;
+    it does not combine with pose_grad yet."""
     if pose_grad and (normal_grad or dist_grad):
         raise Exception("render(pose_grad=True) does not combine with normal_grad / dist_grad yet")
+    antialiasing = bool(getattr(pipe, "antialiasing", False))
+    if pose_grad and antialiasing:
+        raise ValueError("render(pose_grad=True) does not combine with pipe.antialiasing yet (follow-up: camera-pose "
+                         "gradients of an anti-aliased frame)")
     if normal_grad and pipe.compute_cov3D_python:
         raise Exception("render(normal_grad=True) needs the scale/rotation pair (not compute_cov3D_python): "
                         "normals come from the scale axes")
@@ -120,8 +129,9 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         fn = (fused.RasterizeRawParamsDist if dist_grad else fused.RasterizeRawParamsNormal if normal_grad
               else fused.RasterizeRawParamsCamera if pose_grad else fused.RasterizeRawParamsDepth if depth_grad
               else fused.RasterizeRawParams)
-        return _package(screenspace_points, *fn.apply(*raw_args))
-    rasterizer = GaussianRasterizer(raster_settings=raster_settings)
+        with fused._C.antialiased(antialiasing):
+            return _package(screenspace_points, *fn.apply(*raw_args))
+    rasterizer = GaussianRasterizer(raster_settings=raster_settings, antialiasing=antialiasing)
 
     means3D = xyz
     means2D = screenspace_points
@@ -169,15 +179,18 @@ def _package(screenspace_points, rendered_image, radii, depth, alpha=None, norma
 
 
 @torch.no_grad()
-def render_depth_normal(viewpoint_camera, pc, bg_color: torch.Tensor, scaling_modifier=1.0, low_pass=0.3):
+def render_depth_normal(viewpoint_camera, pc, bg_color: torch.Tensor, scaling_modifier=1.0, low_pass=0.3,
+                        pipe=None):
     """Evaluation-time render with the auxiliary outputs of BASELINE configs[4] (depth + normal):
-    {render [3,H,W], depth [1,H,W], normal [3,H,W], radii, visibility_filter}.  No autograd graph."""
+    {render [3,H,W], depth [1,H,W], normal [3,H,W], radii, visibility_filter}.  No autograd graph.
+    `pipe` (optional PipelineParams): its `antialiasing` is honoured."""
     settings = GaussianRasterizationSettings(
         image_height=int(viewpoint_camera.image_height), image_width=int(viewpoint_camera.image_width),
         tanfovx=math.tan(viewpoint_camera.FoVx * 0.5), tanfovy=math.tan(viewpoint_camera.FoVy * 0.5), bg=bg_color,
         scale_modifier=scaling_modifier, viewmatrix=viewpoint_camera.world_view_transform,
         projmatrix=viewpoint_camera.full_proj_transform, sh_degree=pc.active_sh_degree,
         campos=viewpoint_camera.camera_center, prefiltered=False, debug=False, low_pass=low_pass)
-    color, radii, depth, normal = GaussianRasterizer(settings).render_depth_normal(
+    antialiasing = bool(getattr(pipe, "antialiasing", False))
+    color, radii, depth, normal = GaussianRasterizer(settings, antialiasing=antialiasing).render_depth_normal(
         pc.get_xyz, pc.get_opacity, shs=pc.get_features, scales=pc.get_scaling, rotations=pc.get_rotation)
     return {"render": color, "depth": depth, "normal": normal, "radii": radii, "visibility_filter": radii > 0}

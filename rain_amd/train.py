@@ -237,9 +237,20 @@ class Trainer:
         self._geometry_weight(0)  # a non-zero lambda_normal on the sharded paths is refused here already
         self._distortion_weight(0)  # and so is a non-zero lambda_dist
         self._importance_prune_now(0)  # and importance pruning
+        self._antialiasing()  # and pipe.antialiasing
         self.noise_gen = None
         if self._mcmc():  # (checks the options it does not combine with)
             self.noise_gen = torch.Generator(device=dev).manual_seed(self.cfg.seed + 54321)
+
+    def _antialiasing(self) -> bool:
+        """PipelineParams.antialiasing (the opacity compensation of the 2D dilation, RR_FLAG_ANTIALIAS), which
+        the single-GPU steps pass to every frame they render; the sharded steps refuse it."""
+        aa = bool(getattr(self.pipe, "antialiasing", False))
+        if aa and self.sharded:
+            raise ValueError("pipe.antialiasing needs the single-GPU step: the Gaussian-sharded / multi-rank steps "
+                             "have no opacity compensation (rr_preprocess_rows and k_gauss_bwd_views refuse "
+                             "RR_FLAG_ANTIALIAS); train on one GPU or set antialiasing = False")
+        return aa
 
     def _mcmc(self) -> bool:
         """Whether OptimizationParams.densify_strategy selects the MCMC step (rain_amd/mcmc.py); refuses an
@@ -496,7 +507,8 @@ class Trainer:
                 and not lam_t and not self._distortion_weight(iteration + 1)):
             low_pass_now = self.low_pass
             vidx1, cam1 = self._low_pass_and_view(iteration + 1)
-            next_frame = fused.prepare_next(g, cam1, self.background, self.low_pass)
+            next_frame = fused.prepare_next(g, cam1, self.background, self.low_pass,
+                                            antialiasing=self._antialiasing())
             self._pending = [iteration + 1, vidx1, cam1, self.low_pass, next_frame, None]
             self.low_pass = low_pass_now
         with torch.no_grad():
@@ -506,7 +518,8 @@ class Trainer:
             else:
                 image, radii, _depth, st = fused.forward(g, cam, self.background, self.low_pass, cache=cache,
                                                          normal=bool(lam_n),
-                                                         dist=self._dist_range() if lam_t else None)
+                                                         dist=self._dist_range() if lam_t else None,
+                                                         antialiasing=self._antialiasing())
             # loss and dL/dimage in one call (bitwise the separate forward / backward)
             loss, _parts, dimg = l1_ssim_forward_backward(image, gt, opt.lambda_dssim)
             if lam_n or lam_t:
@@ -665,7 +678,8 @@ class Trainer:
                          opacity=g._opacity.grad, scaling=g._scaling.grad, rotation=g._rotation.grad)
             with torch.no_grad():
                 image, _radii, _depth, st = fused.forward(g, cam, self.background, self.low_pass,
-                                                          cache=self._bin_cache if self.reuse_binning else None)
+                                                          cache=self._bin_cache if self.reuse_binning else None,
+                                                          antialiasing=self._antialiasing())
                 loss, _parts, dimg = l1_ssim_forward_backward(image, gt, opt.lambda_dssim)
                 fused.backward(st, dimg, grads, None)
         else:
