@@ -125,6 +125,30 @@ typedef struct rr_frame {
  * rr_preprocess_rows_views and rr_gauss_backward_views (the Gaussian-sharded step). */
 #define RR_FLAG_ANTIALIAS 32
 
+/* Backward only: absolute-gradient densification statistics (AbsGS; gsplat's absgrad=True).
+ * dL/dmeans2D is a signed sum over the pixels a splat touches, and for a large blurry splat the
+ * per-pixel pulls cancel ("gradient collision").  With this flag the blend backward also sums the
+ * magnitudes of the per-pixel terms, in the NDC units of dL_dmeans2D:
+ *
+ *     A[i].x = sum over pixels |dL/dG dG/ddelx| 0.5 W
+ *     A[i].y = sum over pixels |dL/dG dG/ddely| 0.5 H          (so A.x >= |dL_dmeans2D.x| always)
+ *
+ * rr_grads.dL_dmeans2D_abs, if given, receives A ([P,3], z stays 0), and the densification statistics
+ * become grad_accum[i] += sqrt(A.x^2 + A.y^2); denom and max_radii2D behave as without the flag.  Every
+ * other output (dL_dmeans2D, the parameter gradients, the fused Adam step, the next frame's preprocess)
+ * is what the same call gives without the flag.  Rows with radii <= 0 give exact zeros and leave the
+ * statistics untouched; a visible Gaussian no pixel blended gets exactly 0.  With RR_FLAG_ANTIALIAS
+ * the terms see the compensated opacity of the record (dL/dmeans2D itself is unchanged by it).
+ *
+ * Honoured by rr_backward, and by rr_backward_aux / _aux_normal / _aux_dist when every aux map is NULL
+ * (they are rr_backward then), in both parameter modes, with or without rr_grads.adam / .next and
+ * RR_FLAG_WORKSPACE_REGISTERED.  The forward entry points and rr_grads.next->frame accept and ignore
+ * it, so a caller can keep one frame struct.  Refused with RR_ERR_ARG before any device work
+ * (follow-ups): the flag together with a depth / alpha / normal / moments gradient,
+ * rr_backward_camera, rr_backward_records and rr_gauss_backward_views; and a non-NULL
+ * rr_grads.dL_dmeans2D_abs without the flag. */
+#define RR_FLAG_ABSGRAD 64
+
 /* Camera / per-frame device arrays (reference args of the same names). */
 typedef struct rr_camera {
     const float* background; /* [3] */
@@ -243,6 +267,7 @@ typedef struct rr_grads {
     /* Optional, with adam: the NEXT frame's preprocess, run by the per-Gaussian backward on the
      * parameters it has just updated (struct below) */
     const struct rr_next_frame* next;
+    float* dL_dmeans2D_abs; /* [P,3], optional, RR_FLAG_ABSGRAD only; z stays 0 */
 } rr_grads;
 
 /* Cross-step fusion of the training loop: the per-Gaussian backward kernel of step s holds every

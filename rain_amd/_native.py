@@ -36,6 +36,7 @@ RR_FLAG_FULL_BINNING = 4
 RR_FLAG_AUX_NORMAL = 8
 RR_FLAG_WORKSPACE_REGISTERED = 16
 RR_FLAG_ANTIALIAS = 32  # opacity compensation of the 2D dilation (include/rain_raster.h)
+RR_FLAG_ABSGRAD = 64  # backward: absolute mean2D gradient sums and statistics (include/rain_raster.h)
 RR_INCOMPLETE = 4  # rr_forward: stage 1 done, binning buffer too small
 
 
@@ -71,7 +72,8 @@ class RRGrads(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ("dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D",
                                                 "dL_dcov3D", "dL_dsh", "dL_dscales", "dL_drotations",
                                                 "dL_dsh_rest", "grad_accum", "denom", "max_radii2D")] + \
-               [("adam", ctypes.POINTER(RRAdam)), ("next", ctypes.POINTER(RRNextFrame))]
+               [("adam", ctypes.POINTER(RRAdam)), ("next", ctypes.POINTER(RRNextFrame)),
+                ("dL_dmeans2D_abs", ctypes.c_void_p)]  # RR_FLAG_ABSGRAD only
 
 
 class RRCameraGrads(ctypes.Structure):

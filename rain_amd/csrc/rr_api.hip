@@ -833,6 +833,14 @@ int backward_impl(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g
     const int P = f->P, W = f->width, H = f->height, L = num_rendered;
     if (cg && (f->flags & RR_FLAG_ANTIALIAS))
         return fail(RR_ERR_ARG, "RR_FLAG_ANTIALIAS: camera gradients of an anti-aliased frame are not supported yet");
+    const bool absgrad = (f->flags & RR_FLAG_ABSGRAD) != 0;
+    if (absgrad && cg)
+        return fail(RR_ERR_ARG, "RR_FLAG_ABSGRAD: rr_backward_camera is not supported yet");
+    if (absgrad && pg.aux())
+        return fail(RR_ERR_ARG, "RR_FLAG_ABSGRAD: absolute gradients together with a depth / alpha / normal / moments "
+                                "gradient are not supported yet");
+    if (!absgrad && out && out->dL_dmeans2D_abs)
+        return fail(RR_ERR_ARG, "rr_grads.dL_dmeans2D_abs needs RR_FLAG_ABSGRAD");
     if (cg) {  // camera gradients (rr_backward_camera): every refusal before any device work
         if (!cg->dL_dviewmatrix || !cg->dL_dprojmatrix || !cg->dL_dcampos)
             return fail(RR_ERR_ARG, "rr_camera_grads: null gradient output");
@@ -895,7 +903,7 @@ int backward_impl(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g
     }
     hipStream_t st = (hipStream_t)stream;
     float* gacc = static_cast<float*>(workspace);
-    const BwdPlan plan = plan_backward(pg, cg != nullptr);
+    const BwdPlan plan = plan_backward(pg, cg != nullptr, absgrad);
     if (int rc2 = blend_backward(f, cam, geom_buffer, image_buffer, binning_buffer, L, pg, plan.blend, gacc, st))
         return rc2;
     {
@@ -912,6 +920,10 @@ int backward_impl(const rr_frame* f, const rr_camera* cam, const rr_gaussians* g
         a.dL_dscales = out->dL_dscales; a.dL_drot = out->dL_drotations;
         a.dL_dsh_rest = out->dL_dsh_rest;
         if (a.antialias) a.splats = carve_geom(const_cast<void*>(geom_buffer), P).splats;
+        if (absgrad) {  // the absolute sums and the statistics on them in a pass of their own (rr_kernels.hpp)
+            launch_abs_stats(P, gacc, radii, out->dL_dmeans2D_abs, a.grad_accum, a.denom, a.max_radii2D, st);
+            a.grad_accum = nullptr; a.denom = nullptr; a.max_radii2D = nullptr;
+        }
         if (nx) {
             const Geom ng = carve_geom(nx->geom_buffer, P);
             PreArgs n = pre_args(nx->frame, nx->cam, g);
@@ -1097,6 +1109,8 @@ int rr_backward_records(const rr_frame* f, const rr_camera* cam, const int* radi
                         void* workspace, size_t workspace_bytes, int rows_per_rank, int chunk_rows, float* records,
                         void* stream) {
     if (!f || !cam) return fail(RR_ERR_ARG, "null frame / camera");
+    if (f->flags & RR_FLAG_ABSGRAD)
+        return fail(RR_ERR_ARG, "RR_FLAG_ABSGRAD: rr_backward_records (the sharded step) is not supported yet");
     const int P = f->P;
     if (P < 0) return fail(RR_ERR_ARG, "bad P");
     if (rows_per_rank < 0 || (rows_per_rank > 0 && (P % rows_per_rank != 0 || chunk_rows < 1)))
@@ -1121,6 +1135,9 @@ int rr_gauss_backward_views(const rr_frame* f, const rr_view* views, int num_vie
     if (!f || !views || !g || !out) return fail(RR_ERR_ARG, "null argument");
     if (f->flags & RR_FLAG_ANTIALIAS)
         return fail(RR_ERR_ARG, "RR_FLAG_ANTIALIAS: the sharded backward is not supported yet");
+    if (f->flags & RR_FLAG_ABSGRAD)
+        return fail(RR_ERR_ARG, "RR_FLAG_ABSGRAD: rr_gauss_backward_views (the sharded step) is not supported yet");
+    if (out->dL_dmeans2D_abs) return fail(RR_ERR_ARG, "rr_grads.dL_dmeans2D_abs needs RR_FLAG_ABSGRAD");
     if (num_views < 1 || num_views > RR_MAX_VIEWS) return fail(RR_ERR_ARG, "1 <= num_views <= RR_MAX_VIEWS");
     const int P = f->P;
     if (P < 0 || record_rows < P) return fail(RR_ERR_ARG, "bad P / record_rows");

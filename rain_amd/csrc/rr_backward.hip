@@ -1092,6 +1092,36 @@ void launch_pack_records(const float* gacc, const int* radii, int P, int Q, int 
     if (P > 0) k_pack_records<<<(P + 255) / 256, 256, 0, st>>>(gacc, radii, P, Q, chunk_rows, rec);
 }
 
+// RR_FLAG_ABSGRAD (rr_kernels.hpp launch_abs_stats): the absolute mean2D sums out of accumulator slots 13 / 14.
+__global__ __launch_bounds__(256) void k_abs_stats(int P, const float* __restrict__ gacc, const int* __restrict__ radii,
+                                                   float* __restrict__ dabs, float* __restrict__ grad_accum,
+                                                   float* __restrict__ denom, float* __restrict__ max_radii2D) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= P) return;
+    const int radius = radii[i];
+    float sx = 0.f, sy = 0.f;
+    if (radius > 0) {
+        sx = gacc[(size_t)i * GACC_STRIDE + GACC_ABS_X];
+        sy = gacc[(size_t)i * GACC_STRIDE + GACC_ABS_Y];
+    }
+    if (dabs) {
+        dabs[3 * (size_t)i + 0] = sx;
+        dabs[3 * (size_t)i + 1] = sy;
+        dabs[3 * (size_t)i + 2] = 0.f;
+    }
+    if (grad_accum && radius > 0) {  // as gauss_bwd_one's statistics, on |A|
+        grad_accum[i] += sqrtf(sx * sx + sy * sy);
+        denom[i] += 1.0f;
+        max_radii2D[i] = fmaxf(max_radii2D[i], (float)radius);
+    }
+}
+
+void launch_abs_stats(int P, const float* gacc, const int* radii, float* dL_dmeans2D_abs, float* grad_accum,
+                      float* denom, float* max_radii2D, hipStream_t st) {
+    if (P > 0 && (dL_dmeans2D_abs || grad_accum))
+        k_abs_stats<<<(P + 255) / 256, 256, 0, st>>>(P, gacc, radii, dL_dmeans2D_abs, grad_accum, denom, max_radii2D);
+}
+
 // The kernel of (mode, SH degree); kGaussBwdCam has its own launcher below.
 using GaussBwdKernel = void (*)(GaussBwdArgs);
 static const GaussBwdKernel kGaussBwdKernels[3][4] = {

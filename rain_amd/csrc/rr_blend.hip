@@ -68,21 +68,42 @@ namespace rr {
 // bench scene, the spilling build is again the faster one (blend backward 0.314 / 0.300 vs 0.335 /
 // 0.321 ms), so it is built that way (RR_BWD_NDIST_OCC).  The three older
 // modes ignore the three extra arguments and compile to the code they had before.
+//
+// Abs mode (k_blend_bwd<kBlendBwdPlainAbs>, RR_FLAG_ABSGRAD): the plain kernel plus the absolute mean2D
+// sums A.x = sum |v hx|, A.y = sum |v hy| over the pair's active pixels, with v = e dL/dalpha
+// (= dL/dG G) and (hx, hy) = conic . (dx, dy): the magnitudes of the per-pixel terms whose signed sums
+// are components 0 and 1.  The signed ones are linear in v, which is why three moments suffice for
+// them; the magnitudes are not, so they are summed per pixel (two fmas for h, two multiplies and two
+// adds with the abs as a source modifier), become components 9 and 10 of an 11-component pair record
+// (wave_sum22) and go to accumulator slots 13 and 14 (GACC_ABS_X / _Y; slots 9..12 keep their aux
+// meanings, so ABS can be widened to the aux modes later: it is derived from the mode below).  It
+// carries two more sums and the pair's h terms: 128 VGPRs with 28 spilled (116 B of scratch per lane) at 4
+// waves per SIMD, 157 VGPRs without scratch at 3.  Measured interleaved on the bench scene (tools/absgrad_bench.py,
+// profiles/absgrad_bench.json), the build without spills is the faster one here (blend backward 0.2560 / 0.2556
+// vs 0.2637 / 0.2628 ms, against 0.208 ms of the plain kernel), so it is built that way (RR_BWD_ABS_OCC).
+// The five older modes compile to the code they had before.
 // (BlendBwdMode: rr_bwd_plan.hpp)
 #ifndef RR_BWD_NDIST_OCC
 #define RR_BWD_NDIST_OCC 3
 #endif
+#ifndef RR_BWD_ABS_OCC
+#define RR_BWD_ABS_OCC 3
+#endif
 template <int MODE>
-__global__ __launch_bounds__(64, MODE == kBlendBwdPlain ? 4 : MODE == kBlendBwdNormalDist ? RR_BWD_NDIST_OCC : 3)
+__global__ __launch_bounds__(64, MODE == kBlendBwdPlain          ? 4
+                                 : MODE == kBlendBwdPlainAbs     ? RR_BWD_ABS_OCC
+                                 : MODE == kBlendBwdNormalDist   ? RR_BWD_NDIST_OCC
+                                                                 : 3)
 void k_blend_bwd(BlendBwdArgs a, const float* __restrict__ dL_ddepth, const float* __restrict__ dL_dalpha_map,
                  const float* __restrict__ dL_dnormal, const float4* __restrict__ normals,
                  const float* __restrict__ dL_dmoments, float dist_near, float dist_scale) {
-    constexpr bool AUX = MODE != kBlendBwdPlain;
+    constexpr bool ABS = MODE == kBlendBwdPlainAbs;  // the absolute mean2D sums (plain only for now)
+    constexpr bool AUX = MODE != kBlendBwdPlain && MODE != kBlendBwdPlainAbs;
     constexpr bool NRM = MODE == kBlendBwdNormal || MODE == kBlendBwdNormalDist;
     constexpr bool MOM = MODE == kBlendBwdDist || MODE == kBlendBwdNormalDist;
     constexpr int PPL = 4;
     constexpr int B = 64;
-    constexpr int NG = NRM ? NGRAD_NRM : AUX ? NGRAD_AUX : NGRAD;
+    constexpr int NG = ABS ? NGRAD_ABS : NRM ? NGRAD_NRM : AUX ? NGRAD_AUX : NGRAD;
     const int ntiles = a.gx * a.gy;
     const int tile = a.order ? (int)a.order[blockIdx.x] : xcd_tile(blockIdx.x, ntiles);
     const int nmax = (int)a.tile_max[tile];  // pairs past this index were blended by no pixel
@@ -217,6 +238,14 @@ void k_blend_bwd(BlendBwdArgs a, const float* __restrict__ dL_ddepth, const floa
             const float dx = A.x - pfx;
             const P2X px2 = blend_p2_x(A.z, A.w, Bv.y, dx);  // identical to the forward's values
             float sv = 0.f, svdy = 0.f, svdy2 = 0.f;
+            // ABS: sum |v hx|, sum |v hy| with (hx, hy) = conic . (dx, dy); the x parts once per pair
+            [[maybe_unused]] float sax = 0.f, say = 0.f, hx0 = 0.f, hy0 = 0.f, acy = 0.f, acz = 0.f;
+            if constexpr (ABS) {
+                float ccx;
+                splat_conic(A, Bv, ccx, acy, acz);
+                hx0 = ccx * dx;
+                hy0 = acy * dx;
+            }
             const float4 Cc = s_c[j];  // once per pair (not per active row)
             // every pixel's alpha first, in one basic block, so that the PPL exp chains interleave
             // instead of each waiting behind the previous pixel's branched body (LLVM sinks each
@@ -282,6 +311,12 @@ void k_blend_bwd(BlendBwdArgs a, const float* __restrict__ dL_ddepth, const floa
                     sv += v;
                     svdy += vdy;
                     svdy2 = __builtin_fmaf(vdy, dy, svdy2);
+                    if constexpr (ABS) {
+                        const float hx = __builtin_fmaf(acy, dy, hx0);
+                        const float hy = __builtin_fmaf(acz, dy, hy0);
+                        sax += __builtin_fabsf(v * hx);
+                        say += __builtin_fabsf(v * hy);
+                    }
                 }
             }
             // unconditionally: with no active pixel the sums are 0 and so are these (a branch here
@@ -302,6 +337,10 @@ void k_blend_bwd(BlendBwdArgs a, const float* __restrict__ dL_ddepth, const floa
             g[7] = g7;
             g[8] = g8;
             if constexpr (AUX) g[9] = g9;
+            if constexpr (ABS) {
+                g[9] = sax;
+                g[10] = say;
+            }
             if constexpr (NRM) {
                 g[10] = g10;
                 g[11] = g11;
@@ -320,7 +359,11 @@ void k_blend_bwd(BlendBwdArgs a, const float* __restrict__ dL_ddepth, const floa
 #pragma unroll
                 for (int k = 0; k < NG; k++) gb[k] = 0.f;
             }
-            if constexpr (NRM) {
+            if constexpr (ABS) {
+                float t[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                if (__ballot(anya || anyb) != 0ull) wave_sum22(ga, gb, t);
+                red22_store(&s_g[j * NG], lane, t, has_b);
+            } else if constexpr (NRM) {
                 float t[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
                 if (__ballot(anya || anyb) != 0ull) wave_sum26(ga, gb, t);
                 red26_store(&s_g[j * NG], lane, t, has_b);
@@ -349,10 +392,13 @@ void k_blend_bwd(BlendBwdArgs a, const float* __restrict__ dL_ddepth, const floa
                     float ccx, ccy, ccz;
                     splat_conic(s_a[pair], s_b[pair], ccx, ccy, ccz);
                     v = comp == 0 ? -(ccx * sx + ccy * sy) * ddelx_dx : -(ccz * sy + ccy * sx) * ddely_dy;
+                } else if (ABS && comp >= 9) {  // the absolute sums: the NDC factor only
+                    v *= comp == 9 ? ddelx_dx : ddely_dy;
                 } else {
                     v *= comp <= 4 ? -0.5f : 1.f;
                 }
-                if (v != 0.f) atomicAdd(a.gacc + (size_t)s_id[pair] * GACC_STRIDE + comp, v);
+                const int slot = ABS && comp >= 9 ? comp + (GACC_ABS_X - 9) : comp;
+                if (v != 0.f) atomicAdd(a.gacc + (size_t)s_id[pair] * GACC_STRIDE + slot, v);
             }
         }
         __syncthreads();
@@ -459,6 +505,10 @@ void launch_blend_bwd(const BlendBwdArgs& a, const PixelGrads& g, BlendBwdMode m
         case kBlendBwdNormalDist:
             k_blend_bwd<kBlendBwdNormalDist><<<T, 64, 0, st>>>(a, g.dL_ddepth, g.dL_dalpha, g.dL_dnormal, normals,
                                                                g.dL_dmoments, near, scale);
+            break;
+        case kBlendBwdPlainAbs:
+            k_blend_bwd<kBlendBwdPlainAbs><<<T, 64, 0, st>>>(a, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f,
+                                                             0.f);
             break;
     }
 }

@@ -25,6 +25,7 @@ enum BlendBwdMode {
     kBlendBwdNormal = 2,
     kBlendBwdDist = 3,        // depth + moments
     kBlendBwdNormalDist = 4,  // depth + normal + moments
+    kBlendBwdPlainAbs = 5,    // plain + the absolute mean2D sums (RR_FLAG_ABSGRAD; accumulator slots 13, 14)
 };
 
 // The per-Gaussian backward's kernel (rr_backward.hip): k_gauss_bwd, _depth (reads accumulator slot
@@ -43,8 +44,9 @@ struct BwdPlan {
 
 // The one place that picks the variants.  dL_dpix changes neither; the moments ride slot 9, so they
 // need no per-Gaussian variant beyond depth's.  (camera with dL_dnormal / dL_dmoments is refused
-// before this is asked.)
-inline BwdPlan plan_backward(const PixelGrads& g, bool camera) {
+// before this is asked.)  absgrad (RR_FLAG_ABSGRAD): the plain blend becomes its abs variant; the flag
+// with an aux map or camera gradients is refused before this is asked, so every other plan stands.
+inline BwdPlan plan_backward(const PixelGrads& g, bool camera, bool absgrad = false) {
     BwdPlan p;
     if (g.dL_dmoments) p.blend = g.dL_dnormal ? kBlendBwdNormalDist : kBlendBwdDist;
     else if (g.dL_dnormal) p.blend = kBlendBwdNormal;
@@ -52,6 +54,7 @@ inline BwdPlan plan_backward(const PixelGrads& g, bool camera) {
     if (camera) p.gauss = kGaussBwdCam;
     else if (g.dL_dnormal) p.gauss = kGaussBwdNormal;
     else p.gauss = g.aux() ? kGaussBwdDepth : kGaussBwdPlain;
+    if (absgrad && p.blend == kBlendBwdPlain) p.blend = kBlendBwdPlainAbs;
     return p;
 }
 

@@ -29,6 +29,11 @@ constexpr int GACC_STRIDE = 16;            // floats per Gaussian in the backwar
 constexpr int NGRAD = 9;                   // accumulated components per (tile, Gaussian) pair
 constexpr int NGRAD_AUX = 10;              // with depth / alpha gradients: slot 9 = dL/d(view depth)
 constexpr int NGRAD_NRM = 13;              // with a normal gradient too: slots 10..12 = dL/d(normal)
+// RR_FLAG_ABSGRAD: the plain pair record gains the absolute mean2D sums as components 9 and 10, which
+// go to accumulator slots 13 and 14 (slots 9..12 keep their aux meanings)
+constexpr int NGRAD_ABS = 11;
+constexpr int GACC_ABS_X = 13;
+constexpr int GACC_ABS_Y = 14;
 
 struct alignas(16) Splat {
     float4 a;
@@ -569,6 +574,28 @@ __device__ __forceinline__ void red26_store(float* dst, int lane, const float (&
 #pragma unroll
             for (int i = 0; i < 6; i++) d[2 * i + odd] = t[i];
             if (!odd) d[12] = t[6];
+        }
+    }
+}
+// The eleven-component form (the plain + abs blend backward, components 9 and 10 = the absolute mean2D
+// sums): padded to 12, so lane 16r+15 holds component 2i + (r & 1) of pair r >> 1 in t[i] for i < 5, and
+// the even rows (lanes 15 / 47) hold component 10 of a / b in t[5].
+__device__ __forceinline__ void wave_sum22(const float (&a)[NGRAD_ABS], const float (&b)[NGRAD_ABS], float (&t)[6]) {
+    float r[NGRAD_ABS];
+#pragma unroll
+    for (int k = 0; k < NGRAD_ABS; k++) r[k] = swap32_add(a[k], b[k]);
+#pragma unroll
+    for (int i = 0; i < 5; i++) t[i] = row16_sum(swap16_add(r[2 * i], r[2 * i + 1]));
+    t[5] = row16_sum(swap16_add(r[10], 0.f));
+}
+__device__ __forceinline__ void red22_store(float* dst, int lane, const float (&t)[6], bool has_b) {
+    if ((lane & 15) == 15) {
+        const int row = lane >> 4, sel = row >> 1, odd = row & 1;
+        if (sel == 0 || has_b) {
+            float* d = dst + sel * NGRAD_ABS;
+#pragma unroll
+            for (int i = 0; i < 5; i++) d[2 * i + odd] = t[i];
+            if (!odd) d[10] = t[5];
         }
     }
 }

@@ -209,6 +209,14 @@ struct GaussBwdArgs {
     // opacity is o comp
     const Splat* splats;
 };
+// RR_FLAG_ABSGRAD: accumulator slots 13 / 14 (GACC_ABS_X / _Y) hold the absolute mean2D sums A of an abs blend
+// backward.  One thread per Gaussian: dL_dmeans2D_abs (optional, [P,3]) receives (A.x, A.y, 0), exact zeros for
+// radius <= 0, and the densification statistics (optional, all three or none) are updated for radius > 0 as the
+// per-Gaussian backward updates them, with |A| in place of |dL/dmean2D|; that backward is then launched without
+// statistics.  A pass of its own, so that the per-Gaussian backward, the step's largest kernel, stays the code
+// it is without the flag.
+void launch_abs_stats(int P, const float* gacc, const int* radii, float* dL_dmeans2D_abs, float* grad_accum,
+                      float* denom, float* max_radii2D, hipStream_t st);
 // The per-Gaussian backward in `mode` (rr_bwd_plan.hpp; not kGaussBwdCam, which is launch_gauss_bwd_cam):
 // kGaussBwdDepth — the accumulators come from an aux blend backward; slot 9, dL/d(view depth), is read
 // and chained into dL/dmeans3D through the view matrix's z row.  kGaussBwdNormal — slot 9 as above, and
@@ -355,6 +363,7 @@ void launch_mark_visible(int P, const float* means3D, const float* view, uint8_t
 //   normal modes: g.dL_dnormal is the [3,H,W] planar gradient of the aux normal map, `normals` the frame's
 //     per-Gaussian view-space normals (Geom::normals, written by a forward with RR_FLAG_AUX_NORMAL; unused
 //     by the other modes); dL/d(normal) is accumulated into slots 10..12.
+//   kBlendBwdPlainAbs: plain, and the absolute mean2D sums are accumulated into slots 13 and 14.
 //   moment modes: g.dL_dmoments is the [2,H,W] planar gradient of the depth-moment maps (dL/dM1, dL/dM2)
 //     under the mapping g.dist_near / g.dist_far; dL/dm_i times dm/dz is added into slot 9.
 void launch_blend_bwd(const BlendBwdArgs& a, const PixelGrads& g, BlendBwdMode mode, const float4* normals,

@@ -16,6 +16,8 @@ takes a gradient of the aux normal map of ``rasterize_gaussians_aux`` as well (r
 gradients of the camera arrays (viewmatrix, projmatrix, campos; rr_backward_camera).
 ``antialiased()`` makes the calls inside its block render and differentiate anti-aliased frames
 (RR_FLAG_ANTIALIAS: the opacity compensation of the 2D dilation).
+``absgrad()`` makes the backward calls inside its block also sum the absolute per-pixel mean2D gradients
+(RR_FLAG_ABSGRAD; AbsGS, gsplat's ``absgrad``), and ``rasterize_gaussians_backward_abs`` returns them.
 
 Differences that are deliberate and invisible to callers: scratch buffers are sized by the C
 ABI's *_bytes() queries instead of grown through std::function callbacks; outputs the kernels
@@ -92,8 +94,25 @@ def antialiased(on=True):
         _SWITCH.antialiasing = prev
 
 
+# Absolute-gradient densification statistics (include/rain_raster.h RR_FLAG_ABSGRAD): the same kind of
+# switch.  It is a flag of the backward's frame; the forward calls accept and ignore it.
+def absgrad_on() -> bool:
+    return bool(getattr(_SWITCH, "absgrad", False))
+
+
+@contextlib.contextmanager
+def absgrad(on=True):
+    prev = absgrad_on()
+    _SWITCH.absgrad = bool(on)
+    try:
+        yield
+    finally:
+        _SWITCH.absgrad = prev
+
+
 def _frame(P, degree, M, W, H, tan_fovx, tan_fovy, scale_modifier, low_pass, prefiltered, debug):
-    flags = frame_flags() | (N.RR_FLAG_ANTIALIAS if antialiasing_on() else 0)
+    flags = frame_flags() | (N.RR_FLAG_ANTIALIAS if antialiasing_on() else 0) | \
+        (N.RR_FLAG_ABSGRAD if absgrad_on() else 0)
     return N.RRFrame(int(P), int(degree), int(M), int(W), int(H), float(tan_fovx), float(tan_fovy),
                      float(scale_modifier), float(low_pass), int(bool(prefiltered)), int(bool(debug)), flags)
 
@@ -203,6 +222,19 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                      dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, low_pass)
 
 
+def rasterize_gaussians_backward_abs(background, means3D, radii, colors, scales, rotations, scale_modifier,
+                                     cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh,
+                                     degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, low_pass):
+    """rasterize_gaussians_backward with RR_FLAG_ABSGRAD: its 8 tensors (unchanged) plus dL_dmeans2D_abs
+    [P,3], the sums over a Gaussian's pixels of the absolute per-pixel dL/dmeans2D terms (z stays 0;
+    no reference counterpart).  A 9-tuple."""
+    with absgrad(True):
+        return _backward("rasterize_gaussians_backward_abs", background, means3D, radii, colors, scales,
+                         rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy,
+                         dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, low_pass,
+                         want_abs=True)
+
+
 def rasterize_gaussians_backward_depth(background, means3D, radii, colors, scales, rotations, scale_modifier,
                                        cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh,
                                        degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, low_pass,
@@ -278,7 +310,7 @@ def _present(t):
 def _backward(label, background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
               projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
               imageBuffer, debug, low_pass, dL_dout_depth=None, dL_dout_alpha=None, dL_dout_normal=None,
-              dL_dout_moments=None, dist=(0.0, 0.0), camera=False):
+              dL_dout_moments=None, dist=(0.0, 0.0), camera=False, want_abs=False):
     """Every rasterize_gaussians_backward* above (`label`: its name, for error messages).  An absent map
     goes to the library as NULL, and the library picks the kernel variants from which maps are there."""
     P = means3D.size(0)
@@ -301,7 +333,7 @@ def _backward(label, background, means3D, radii, colors, scales, rotations, scal
     if P == 0:
         z = lambda *s: torch.zeros(s, **fopts)  # noqa: E731
         return (z(0, 3), z(0, NUM_CHANNELS), z(0, 1), z(0, 3), z(0, 6), z(0, M, 3), z(0, 3), z(0, 4)) + \
-            ((z(4, 4), z(4, 4), z(3)) if camera else ())
+            ((z(4, 4), z(4, 4), z(3)) if camera else ()) + ((z(0, 3),) if want_abs else ())
     L = N.raster()
     keep = dict(
         bg=_dev_f32(background, device, "bg"), means3D=_dev_f32(means3D, device, "means3D"),
@@ -322,6 +354,9 @@ def _backward(label, background, means3D, radii, colors, scales, rotations, scal
     res = tuple(torch.empty(shape, **fopts)
                 for shape in ((P, 3), (P, NUM_CHANNELS), (P, 1), (P, 3), (P, 6), (P, M, 3), (P, 3), (P, 4)))
     grads = N.RRGrads(*[_ptr(t) for t in res])
+    if want_abs:
+        res = res + (torch.empty((P, 3), **fopts),)
+        grads.dL_dmeans2D_abs = _ptr(res[8])
     ws = torch.empty((L.rr_backward_workspace_bytes(P),), dtype=torch.uint8, device=device)
     head = (ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs), _ptr(keep["radii"]), _ptr(geomBuffer),
             _ptr(imageBuffer), _ptr(binningBuffer), int(R), _ptr(dpix))

@@ -23,6 +23,8 @@ _MSG_COV = 'Please provide exactly one of either scale/rotation pair or precompu
 _MSG_DIST = 'forward_distortion needs 0 < dist_near < dist_far, or both 0 (metric depth)'
 _MSG_AA_CAMERA = ('forward_camera does not combine with antialiasing yet (follow-up: camera-pose gradients of an '
                   'anti-aliased frame, RR_FLAG_ANTIALIAS)')
+_MSG_ABS = ('{} does not combine with absgrad yet (follow-up: absolute-gradient statistics together with {}, '
+            'RR_FLAG_ABSGRAD)')
 _MSG_NORMAL = 'render_depth_normal needs the scale/rotation pair (normals come from the scale axes)'
 
 
@@ -54,6 +56,21 @@ def _antialiased(on):
 
 def _antialiasing_on():
     fn = getattr(_C, "antialiasing_on", None)
+    return bool(fn is not None and fn())
+
+
+def _absgrad(on):
+    """_C.absgrad(on): the backward calls inside the block also sum the absolute mean2D gradients.  A stand-in
+    `_C` without the switch serves the signed gradients only."""
+    if hasattr(_C, "absgrad"):
+        return _C.absgrad(on)
+    if on:
+        raise RuntimeError("absgrad needs the rasterizer's own _C (this one has no absgrad() switch)")
+    return contextlib.nullcontext()
+
+
+def _absgrad_on():
+    fn = getattr(_C, "absgrad_on", None)
     return bool(fn is not None and fn())
 
 
@@ -104,6 +121,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.raster_settings = s
         ctx.num_rendered = num_rendered
         ctx.antialiasing = _antialiasing_on()  # the frame's switch (_C.antialiased), for its backward
+        ctx.absgrad = _absgrad_on()  # (_C.absgrad) the backward then leaves means2D.absgrad, gsplat's convention
+        ctx.means2D = means2D if ctx.absgrad else None  # a plain reference: the attribute goes on this object
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning,
                               img)
         return color, radii, depth
@@ -113,10 +132,13 @@ class _RasterizeGaussians(torch.autograd.Function):
         # depth receives no gradient: grad_depth is accepted and dropped (__init__.py:91-120)
         s = ctx.raster_settings
         args = _backward_args(s, ctx.saved_tensors, ctx.num_rendered, grad_out_color)
-        with _antialiased(ctx.antialiasing):
-            d_means2D, d_colors, d_opacities, d_means3D, d_cov3D, d_sh, d_scales, d_rotations = _invoke(
-                _C.rasterize_gaussians_backward, args, s.debug, "snapshot_bw.dump",
+        with _antialiased(ctx.antialiasing), _absgrad(ctx.absgrad):
+            d_means2D, d_colors, d_opacities, d_means3D, d_cov3D, d_sh, d_scales, d_rotations, *d_abs = _invoke(
+                _C.rasterize_gaussians_backward_abs if ctx.absgrad else _C.rasterize_gaussians_backward, args,
+                s.debug, "snapshot_bw.dump",
                 "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
+        if ctx.absgrad:  # [P,3], the absolute sums beside the signed .grad
+            ctx.means2D.absgrad = d_abs[0]
         # order of forward()'s inputs; raster_settings gets None
         return d_means3D, d_means2D, d_sh, d_colors, d_opacities, d_scales, d_rotations, d_cov3D, None
 
@@ -271,6 +293,13 @@ def _checked_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp, norma
 
 
 class GaussianRasterizer(nn.Module):
+    # Absolute-gradient densification statistics (AbsGS, gsplat's absgrad; include/rain_raster.h
+    # RR_FLAG_ABSGRAD): set on the instance after construction (r.absgrad = True).  forward()'s backward then
+    # leaves means2D.absgrad [P,3], the per-pixel absolute dL/dmeans2D sums, beside means2D.grad (unchanged).
+    # Left False, forward() follows the thread's `_C.absgrad()` switch instead.
+    # The other forward_* methods and render_depth_normal refuse it (follow-ups).
+    absgrad = False
+
     def __init__(self, raster_settings, antialiasing=False):
         """antialiasing (upstream 3DGS's name; it travels beside the 13 settings fields): every splat's
         opacity is scaled by sqrt(max(0.000025, det(cov2D) / det(cov2D + low_pass I))), the opacity
@@ -290,7 +319,8 @@ class GaussianRasterizer(nn.Module):
                 cov3D_precomp=None):
         shs, colors_precomp, scales, rotations, cov3D_precomp = _checked_inputs(shs, colors_precomp, scales,
                                                                                 rotations, cov3D_precomp)
-        with _antialiased(self.antialiasing):
+        # .absgrad only ever turns the switch on: a caller's own `with _C.absgrad():` block around this call stands
+        with _antialiased(self.antialiasing), (_absgrad(True) if self.absgrad else contextlib.nullcontext()):
             return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                        cov3D_precomp, self.raster_settings)
 
@@ -301,6 +331,8 @@ class GaussianRasterizer(nn.Module):
         sum alpha_i T_i z_i (no background term, not normalised), alpha is 1 - T_final =
         sum alpha_i T_i; expected depth is depth / alpha.  Gradient conventions are the colour
         path's (no mask for the 0.99 alpha clamp, dL/dmeans2D in NDC units)."""
+        if self.absgrad:
+            raise ValueError(_MSG_ABS.format("forward_depth", "depth / alpha gradients"))
         shs, colors_precomp, scales, rotations, cov3D_precomp = _checked_inputs(shs, colors_precomp, scales,
                                                                                 rotations, cov3D_precomp)
         with _antialiased(self.antialiasing):
@@ -319,6 +351,8 @@ class GaussianRasterizer(nn.Module):
         A rasterizer built with antialiasing=True raises a ValueError (a follow-up)."""
         if self.antialiasing:
             raise ValueError(_MSG_AA_CAMERA)
+        if self.absgrad:
+            raise ValueError(_MSG_ABS.format("forward_camera", "camera-pose gradients"))
         shs, colors_precomp, scales, rotations, cov3D_precomp = _checked_inputs(shs, colors_precomp, scales,
                                                                                 rotations, cov3D_precomp)
         s = self.raster_settings
@@ -333,6 +367,8 @@ class GaussianRasterizer(nn.Module):
         camera; no background term).  Its gradient reaches the rotations directly (the axis choice
         and the flip are constants) and opacity, position and covariance through alpha_i.  Needs the
         scale/rotation pair (cov3D_precomp is refused)."""
+        if self.absgrad:
+            raise ValueError(_MSG_ABS.format("forward_normal", "a normal-map gradient"))
         shs, colors_precomp, scales, rotations, cov3D_precomp = _checked_inputs(
             shs, colors_precomp, scales, rotations, cov3D_precomp, normal=True)
         with _antialiased(self.antialiasing):
@@ -348,6 +384,8 @@ class GaussianRasterizer(nn.Module):
         itself for dist_near = dist_far = 0.  The per-pixel distortion sum_{i>j} w_i w_j (m_i - m_j)^2 is
         alpha * M2 - M1^2 (rain_amd.loss.fused_distortion_loss).  With `normal` the aux normal map of
         forward_normal() is rendered and differentiated too (needs the scale/rotation pair)."""
+        if self.absgrad:
+            raise ValueError(_MSG_ABS.format("forward_distortion", "depth-moment gradients"))
         shs, colors_precomp, scales, rotations, cov3D_precomp = _checked_inputs(
             shs, colors_precomp, scales, rotations, cov3D_precomp, normal=normal)
         near, far = float(dist_near), float(dist_far)
@@ -381,6 +419,8 @@ class GaussianRasterizer(nn.Module):
         radii [P], depth [1,H,W], normal [3,H,W]).  The normal map (no reference counterpart) blends
         each Gaussian's view-space smallest-scale axis, facing the camera, like depth: sum of
         alpha*T*n, no background (include/rain_raster.h RR_FLAG_AUX_NORMAL).  Needs scales/rotations."""
+        if self.absgrad:
+            raise ValueError(_MSG_ABS.format("render_depth_normal", "the aux normal frame"))
         if (shs is None) == (colors_precomp is None):
             raise Exception(_MSG_COLOR)
         if scales is None or rotations is None:

@@ -276,7 +276,7 @@ def backward(st: RawFrame, dL_dpix: torch.Tensor, grads: dict | None, stats: tup
              adam: "N.RRAdam | None" = None, dmeans2D: torch.Tensor | None = None, next_frame: NextFrame | None = None,
              dL_ddepth: torch.Tensor | None = None, dL_dalpha: torch.Tensor | None = None,
              dL_dnormal: torch.Tensor | None = None, dL_dmoments: torch.Tensor | None = None,
-             cam_grads: tuple | None = None):
+             cam_grads: tuple | None = None, absgrad: bool = False, dmeans2D_abs: torch.Tensor | None = None):
     """Write dLoss/d(raw parameter) into grads['xyz'|'f_dc'|'f_rest'|'opacity'|'scaling'|'rotation']
     (contiguous fp32 tensors of the parameter shapes, fully overwritten) and, if `stats` =
     (grad_accum [P,1], denom [P,1], max_radii2D [P]) is given, update the densification statistics
@@ -299,7 +299,23 @@ def backward(st: RawFrame, dL_dpix: torch.Tensor, grads: dict | None, stats: tup
     `cam_grads` = (d_viewmatrix [4,4], d_projmatrix [4,4], d_campos [3]) (contiguous fp32, optional): they
     receive the gradients of the frame's three camera arrays (rr_backward_camera), fully overwritten.
     Colour, depth and alpha gradients only, and no `adam` / `next_frame`, and not on a frame rendered with
-    antialiasing (a follow-up)."""
+    antialiasing (a follow-up).
+    `absgrad` (RR_FLAG_ABSGRAD; AbsGS, gsplat's absgrad): the blend backward also sums the absolute per-pixel
+    mean-gradient terms; `stats` then accumulates the norm of those sums instead of the signed gradient's, and
+    `dmeans2D_abs` ([P,3] contiguous fp32, optional) receives them (z = 0).  Every other output is unchanged.
+    Colour gradient only: no aux map and no `cam_grads` (follow-ups)."""
+    if absgrad:
+        if dL_ddepth is not None or dL_dalpha is not None or dL_dnormal is not None or dL_dmoments is not None:
+            raise RuntimeError("rain_amd.fused.backward: absgrad does not combine with depth / alpha / normal / "
+                               "moments gradients yet (RR_FLAG_ABSGRAD)")
+        if cam_grads is not None:
+            raise RuntimeError("rain_amd.fused.backward: absgrad does not combine with camera gradients yet "
+                               "(RR_FLAG_ABSGRAD)")
+    elif dmeans2D_abs is not None:
+        raise RuntimeError("rain_amd.fused.backward: dmeans2D_abs needs absgrad=True")
+    if dmeans2D_abs is not None and (dmeans2D_abs.dtype != torch.float32 or not dmeans2D_abs.is_contiguous() or
+                                     st is None or tuple(dmeans2D_abs.shape) != (st.P, 3)):
+        raise RuntimeError("rain_amd.fused: dmeans2D_abs must be a contiguous float32 [P, 3] tensor")
     if cam_grads is not None:
         if st is not None and st.frame.flags & N.RR_FLAG_ANTIALIAS:
             raise RuntimeError("rain_amd.fused.backward: camera gradients do not combine with antialiasing yet "
@@ -348,7 +364,7 @@ def backward(st: RawFrame, dL_dpix: torch.Tensor, grads: dict | None, stats: tup
     out = N.RRGrads(_p(dmeans2D), None, _p(grads["opacity"]), _p(grads["xyz"]), None, _p(grads["f_dc"]),
                     _p(grads["scaling"]), _p(grads["rotation"]), _p(grads["f_rest"]), _p(acc), _p(den), _p(mr),
                     ctypes.pointer(adam) if adam is not None else None,
-                    ctypes.pointer(next_frame.desc) if next_frame is not None else None)
+                    ctypes.pointer(next_frame.desc) if next_frame is not None else None, _p(dmeans2D_abs))
     dev = dpix.device
     frame = st.frame
     if st.ws is not None:  # zero-filled by the forward render: the backward skips its clear
@@ -357,6 +373,10 @@ def backward(st: RawFrame, dL_dpix: torch.Tensor, grads: dict | None, stats: tup
         frame.flags |= N.RR_FLAG_WORKSPACE_REGISTERED
     else:
         ws = torch.empty((L.rr_backward_workspace_bytes(st.P),), dtype=torch.uint8, device=dev)
+    if absgrad:  # a flag of this backward, on the frame copy
+        if frame is st.frame:
+            frame = N.RRFrame.from_buffer_copy(st.frame)
+        frame.flags |= N.RR_FLAG_ABSGRAD
     head = (ctypes.byref(frame), ctypes.byref(st.cam), ctypes.byref(st.gs), _p(st.radii), _p(st.geom), _p(st.img),
             _p(st.binning), st.num_rendered, _p(dpix) if dL_dpix is not None else None)
     tail = (_p(ws), ws.numel(), ctypes.byref(out))
@@ -395,6 +415,11 @@ def _raw_forward(ctx, inputs, aux=True, normal=False, dist=None, camera=False):
     camera arrays are differentiable inputs.  Inside `with _C.antialiased():` (the classes keep their 18
     inputs, so the switch travels beside them) the frame, and with it its backward, carries RR_FLAG_ANTIALIAS."""
     antialiasing = _C.antialiasing_on()
+    ctx.absgrad = _C.absgrad_on()  # (_C.absgrad) the backward then leaves means2D.absgrad
+    if ctx.absgrad and (aux or camera):
+        raise ValueError("render(absgrad=True) does not combine with depth_grad / normal_grad / dist_grad / "
+                         "pose_grad yet (follow-up: absolute-gradient statistics with those gradients)")
+    ctx.means2D = inputs[6] if ctx.absgrad else None  # a plain reference: the attribute goes on this object
     if camera and antialiasing:
         raise ValueError("render(pose_grad=True) does not combine with antialiasing yet (follow-up: camera-pose "
                          "gradients of an anti-aliased frame)")
@@ -452,8 +477,11 @@ def _raw_backward(ctx, n_inputs, grad_color, grad_depth=None, grad_alpha=None, g
     cg = None
     if camera and any(ctx.needs_input_grad[12:15]):  # else a fixed camera: the plain depth backward
         cg = (torch.empty((4, 4), **fo), torch.empty((4, 4), **fo), torch.empty((3,), **fo))
+    dabs = torch.empty((P, 3), **fo) if ctx.absgrad else None
     backward(st, grad_color, grads, dmeans2D=d2, dL_ddepth=grad_depth, dL_dalpha=grad_alpha, dL_dnormal=grad_normal,
-             dL_dmoments=grad_moments, cam_grads=cg)
+             dL_dmoments=grad_moments, cam_grads=cg, absgrad=ctx.absgrad, dmeans2D_abs=dabs)
+    if ctx.absgrad:  # [P,3], gsplat's convention, beside the signed .grad
+        ctx.means2D.absgrad = dabs
     # (in the inputs' own shapes: a flat [16] matrix gets a flat gradient)
     d_cam = tuple(g.view(s) for g, s in zip(cg, ctx.cam_shapes)) if cg is not None else (None,) * 3
     return (grads["xyz"], grads["f_dc"], grads["f_rest"], grads["opacity"], grads["scaling"], grads["rotation"], d2,

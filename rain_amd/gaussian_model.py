@@ -98,6 +98,13 @@ class OptimizationParams:
         self.densify_from_iter = 500
         self.densify_until_iter = 15_000
         self.densify_grad_threshold = 0.0002
+        # opt-in (AbsGS; gsplat's absgrad): the densification statistic accumulates the norm of the summed
+        # absolute per-pixel dL/dmeans2D terms instead of the norm of their signed sum, which cancels for the
+        # large blurry splats that most need splitting (include/rain_raster.h RR_FLAG_ABSGRAD).  Absolute
+        # gradients are several times larger, so densify_grad_threshold must be raised with it (AbsGS uses
+        # 0.0004, gsplat suggests 0.0008); the default threshold is not changed.  Single-GPU steps, the
+        # "default" strategy, and no lambda_normal / lambda_dist (refused at construction otherwise).
+        self.densify_absgrad = False
         self.random_background = False
         # opt-in (no reference counterpart): weight of the depth-normal consistency term
         # (rain_amd.loss.fused_geometry_loss) added to the loss from `lambda_normal_from_iter` on
@@ -636,12 +643,13 @@ class GaussianModel:
 
         return mcmc.add_new(self, cap_max, generator=generator, min_opacity=min_opacity)
 
-    def add_densification_stats(self, viewspace_point_tensor, update_filter):
-        """gaussian_model.py:419-421 (consumes the NDC-space dL/dmeans2D the rasterizer returns).
+    def add_densification_stats(self, viewspace_point_tensor, update_filter, absgrad=False):
+        """gaussian_model.py:419-421 (consumes the NDC-space dL/dmeans2D the rasterizer returns; with
+        `absgrad` the absolute sums the backward left in viewspace_point_tensor.absgrad instead).
         The reference's boolean-mask indexing makes the host wait for the device (the mask's count
         sizes the gather); the same update as a select keeps the step free of host syncs: masked
         rows gain exactly the reference's norm, the others exactly 0."""
-        g = viewspace_point_tensor.grad
+        g = viewspace_point_tensor.absgrad if absgrad else viewspace_point_tensor.grad
         if g.is_cuda and self._stats_native(g, update_filter):  # one launch (rain_train.h rt_densify_stats)
             from . import _native
             _native.check_rt(_native.train_lib().rt_densify_stats(

@@ -73,7 +73,7 @@ class PipelineParams:
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
            low_pass=0.3, depth_grad=False, normal_grad=False, dist_grad=False, dist_near=0.2, dist_far=100.0,
-           pose_grad=False):
+           pose_grad=False, absgrad=False):
     """The reference's render(); `depth_grad` adds a differentiable "depth" and "alpha" to the
     dictionary, `normal_grad` (which implies depth_grad) a differentiable aux "normal" map [3,H,W]
     as well (sum alpha_i T_i n_i, GaussianRasterizer.forward_normal).  `dist_grad` (which implies
@@ -85,7 +85,13 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     and camera_center reach whatever produced them (rain_amd.cameras.CameraPose;
     GaussianRasterizer.forward_camera).  pipe.antialiasing renders anti-aliased (every splat's opacity times
     sqrt(det cov2D / det(cov2D + low_pass I)), with the factor's gradient; RR_FLAG_ANTIALIAS) on either route;
-    it does not combine with pose_grad yet."""
+    it does not combine with pose_grad yet.  `absgrad` (AbsGS, gsplat's absgrad; RR_FLAG_ABSGRAD): after
+    backward, viewspace_points.absgrad [P,3] holds the sums of the absolute per-pixel dL/dmeans2D terms beside
+    the signed viewspace_points.grad (GaussianModel.add_densification_stats(absgrad=True) reads it); not with
+    depth_grad / normal_grad / dist_grad / pose_grad yet."""
+    if absgrad and (depth_grad or normal_grad or dist_grad or pose_grad):
+        raise ValueError("render(absgrad=True) does not combine with depth_grad / normal_grad / dist_grad / "
+                         "pose_grad yet (follow-up: absolute-gradient statistics with those gradients)")
     if pose_grad and (normal_grad or dist_grad):
         raise Exception("render(pose_grad=True) does not combine with normal_grad / dist_grad yet")
     antialiasing = bool(getattr(pipe, "antialiasing", False))
@@ -129,9 +135,10 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         fn = (fused.RasterizeRawParamsDist if dist_grad else fused.RasterizeRawParamsNormal if normal_grad
               else fused.RasterizeRawParamsCamera if pose_grad else fused.RasterizeRawParamsDepth if depth_grad
               else fused.RasterizeRawParams)
-        with fused._C.antialiased(antialiasing):
+        with fused._C.antialiased(antialiasing), fused._C.absgrad(bool(absgrad)):
             return _package(screenspace_points, *fn.apply(*raw_args))
     rasterizer = GaussianRasterizer(raster_settings=raster_settings, antialiasing=antialiasing)
+    rasterizer.absgrad = bool(absgrad)
 
     means3D = xyz
     means2D = screenspace_points

@@ -238,6 +238,8 @@ class Trainer:
         self._distortion_weight(0)  # and so is a non-zero lambda_dist
         self._importance_prune_now(0)  # and importance pruning
         self._antialiasing()  # and pipe.antialiasing
+        # and densify_absgrad (also refused with the geometry terms and under "mcmc"); decided once, here
+        self._absgrad_on = self._absgrad()
         self.noise_gen = None
         if self._mcmc():  # (checks the options it does not combine with)
             self.noise_gen = torch.Generator(device=dev).manual_seed(self.cfg.seed + 54321)
@@ -251,6 +253,25 @@ class Trainer:
                              "have no opacity compensation (rr_preprocess_rows and k_gauss_bwd_views refuse "
                              "RR_FLAG_ANTIALIAS); train on one GPU or set antialiasing = False")
         return aa
+
+    def _absgrad(self) -> bool:
+        """OptimizationParams.densify_absgrad (AbsGS; RR_FLAG_ABSGRAD): the single-GPU steps feed
+        xyz_gradient_accum with the norm of the absolute per-pixel mean-gradient sums.  Refused where the
+        statistic cannot be formed yet or is not used."""
+        opt = self.opt
+        if not bool(getattr(opt, "densify_absgrad", False)):
+            return False
+        if self.sharded:
+            raise ValueError("densify_absgrad needs the single-GPU step: the Gaussian-sharded / multi-rank steps "
+                             "carry no absolute sums (rr_backward_records and rr_gauss_backward_views refuse "
+                             "RR_FLAG_ABSGRAD); train on one GPU or set densify_absgrad = False")
+        if getattr(opt, "densify_strategy", "default") == "mcmc":
+            raise ValueError("densify_absgrad does not combine with densify_strategy 'mcmc': that strategy uses no "
+                             "gradient statistic; set densify_absgrad = False")
+        if any(float(getattr(opt, k, 0.0) or 0.0) != 0.0 for k in ("lambda_normal", "lambda_dist")):
+            raise ValueError("densify_absgrad does not combine with lambda_normal / lambda_dist yet (follow-up: "
+                             "absolute sums in the depth / normal / moment backward variants); set both to 0")
+        return True
 
     def _mcmc(self) -> bool:
         """Whether OptimizationParams.densify_strategy selects the MCMC step (rain_amd/mcmc.py); refuses an
@@ -541,7 +562,9 @@ class Trainer:
                 fused.backward(st, dimg, grads, stats, adam=adam, dL_ddepth=dD, dL_dalpha=dA, dL_dnormal=dN,
                                dL_dmoments=dM)
             else:
-                fused.backward(st, dimg, grads, stats, adam=adam, next_frame=next_frame)
+                # (the absolute sums only feed the statistics: past the densify phase the plain backward runs)
+                fused.backward(st, dimg, grads, stats, adam=adam, next_frame=next_frame,
+                               absgrad=self._absgrad_on and stats is not None)
             densified = self._finish(iteration, flat, densify_now, reset_now, adam_done=fuse_adam)
         if prune_now:  # after the optimizer step; no next-frame geometry was prepared
             self._importance_prune()
@@ -616,6 +639,7 @@ class Trainer:
         vidx, cam = self._low_pass_and_view(iteration)
         densify_phase = iteration < opt.densify_until_iter
         densify_now, reset_now = self._events(iteration)
+        absgrad = self._absgrad_on and densify_phase  # the absolute sums only feed the statistics
         if self.sharded:  # gradients accumulate into the flat buffer the exchange reduces
             g.pack_flat_state(self.world)
             flat = g.bind_flat_grad(pad_to=self.world)
@@ -629,7 +653,8 @@ class Trainer:
             pkg = render(cam, g, self.pipe, self.background, low_pass=self.low_pass, normal_grad=bool(lam_n),
                          dist_grad=True, dist_near=near, dist_far=far)
         else:
-            pkg = render(cam, g, self.pipe, self.background, low_pass=self.low_pass, normal_grad=bool(lam_n))
+            pkg = render(cam, g, self.pipe, self.background, low_pass=self.low_pass, normal_grad=bool(lam_n),
+                         absgrad=absgrad)
         image, vsp, vis, radii = pkg["render"], pkg["viewspace_points"], pkg["visibility_filter"], pkg["radii"]
         gt = self.gt[vidx]
         # (1-λ)·L1 + λ·(1-SSIM) (train.py:113-114), by default one fused HIP forward/backward
@@ -645,7 +670,7 @@ class Trainer:
         with torch.no_grad():
             if densify_phase:  # train.py:132-134, per rank (merged by _finish when densify runs)
                 g.update_max_radii(radii, vis)
-                g.add_densification_stats(vsp, vis)
+                g.add_densification_stats(vsp, vis, absgrad=absgrad)
             densified = self._finish(iteration, flat, densify_now, reset_now)
         if prune_now:
             self._importance_prune()
