@@ -158,7 +158,8 @@ def raster():
                                  ctypes.POINTER(sz), vp, vp, vp]
         # the backward ladder: every entry is rr_backward with more maps after dL_dpix (dL_ddepth, dL_dalpha;
         # then dL_dnormal; then dL_dmoments, dist_near, dist_far), rr_backward_camera is rr_backward_aux with
-        # the camera-gradient block before the stream
+        # the camera-gradient block before the stream (_raster_driver.backward picks the entry and builds
+        # its argument tuple)
         cf, grp = ctypes.c_float, ctypes.POINTER(RRGrads)
         head = [fp, cp, gp, vp, vp, vp, vp, ci, vp]  # ..., geom, image, binning, num_rendered, dL_dpix
         tail = [vp, sz, grp, vp]                     # workspace, workspace_bytes, out, stream

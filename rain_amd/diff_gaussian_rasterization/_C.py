@@ -24,6 +24,10 @@ ABI's *_bytes() queries instead of grown through std::function callbacks; output
 write completely are allocated with torch.empty (the reference zero-fills them first); scratch and
 outputs live on ``means3D.device`` and kernels run on torch's current stream of that device (the
 reference uses the current device and the legacy default stream).
+
+This module holds the reference signatures, the dtype / device checks, the output allocation, the P == 0
+results and the thread switches; the native call sequences (the counted two-stage forward, the choice of
+backward entry point) are rain_amd/_raster_driver.py's.
 """
 from __future__ import annotations
 
@@ -35,6 +39,8 @@ import threading
 import torch
 
 from .. import _native as N
+from .. import _raster_driver as driver
+from .._raster_driver import ptr as _ptr  # (tests and tools import it from here under this name)
 
 NUM_CHANNELS = 3
 
@@ -48,13 +54,6 @@ EARLY_STOP = os.environ.get("RAIN_EARLY_STOP", "1") != "0"
 
 def frame_flags():
     return (0 if TILE_CULLING else N.RR_FLAG_NO_TILE_CULLING) | (0 if EARLY_STOP else N.RR_FLAG_FULL_BINNING)
-
-
-def _ptr(t):
-    """Device pointer of a tensor, or None for an empty ("absent") tensor (nullptr in the reference)."""
-    if t is None or t.numel() == 0:
-        return None
-    return ctypes.c_void_p(t.data_ptr())
 
 
 def _dev_f32(t, device, name):
@@ -180,38 +179,22 @@ def _rasterize(background, means3D, colors, opacity, scales, rotations, scale_mo
     frame = _frame(P, degree, M, W, H, tan_fovx, tan_fovy, scale_modifier, low_pass, prefiltered, debug)
     if normal:
         frame.flags |= N.RR_FLAG_AUX_NORMAL
-    cam = N.RRCamera(_ptr(keep["bg"]), _ptr(keep["view"]), _ptr(keep["proj"]), _ptr(keep["campos"]))
+    _cam_keep, cam = driver.camera_block(keep["bg"], keep["view"], keep["proj"], keep["campos"])
     gs = N.RRGaussians(_ptr(keep["means3D"]), _ptr(keep["sh"]), _ptr(keep["colors"]), _ptr(keep["opacity"]),
                        _ptr(keep["scales"]), _ptr(keep["rotations"]), _ptr(keep["cov3D"]))
     out_color = torch.empty((NUM_CHANNELS, H, W), **fopts)
     out_depth = torch.empty((1, H, W), **fopts)
     out_normal = torch.empty((3, H, W), **fopts) if normal else None
+    moments = torch.empty((2, H, W), **fopts) if dist is not None else None
     radii = torch.empty((P,), dtype=torch.int32, device=device)
     geom = torch.empty((L.rr_geometry_bytes(P),), **u8)
     img = torch.empty((L.rr_image_bytes(W, H),), **u8)
-    stream = N.stream_of(means3D)
-    nr = ctypes.c_int(0)
-    npairs = ctypes.c_int(0)
-    N.check(L.rr_forward_geometry(ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs), _ptr(radii),
-                                  _ptr(geom), geom.numel(), _ptr(img), img.numel(), ctypes.byref(nr),
-                                  ctypes.byref(npairs), stream),
-            "rasterize_gaussians")
-    num_rendered, num_pairs = nr.value, npairs.value
-    binning = torch.empty((L.rr_binning_bytes(num_pairs, W, H) if num_pairs > 0 else 0,), **u8)
-    if dist is not None:
-        moments = torch.empty((2, H, W), **fopts)
-        N.check(L.rr_forward_render_dist(ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs), _ptr(radii),
-                                         _ptr(geom), _ptr(img), _ptr(binning), binning.numel(), num_pairs,
-                                         _ptr(out_color), _ptr(out_depth), _ptr(out_normal), _ptr(moments),
-                                         dist[0], dist[1], stream),
-                "rasterize_gaussians_dist")
-        return num_rendered, out_color, radii, out_depth, out_normal, geom, binning, img, moments
-    N.check(L.rr_forward_render_aux(ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs), _ptr(radii),
-                                    _ptr(geom), _ptr(img), _ptr(binning), binning.numel(), num_pairs,
-                                    _ptr(out_color), _ptr(out_depth), _ptr(out_normal), stream),
-            "rasterize_gaussians")
     # num_rendered is the reference's value (sum of bounding-square tile counts)
-    return num_rendered, out_color, radii, out_depth, out_normal, geom, binning, img
+    binning, num_rendered = driver.render_counted(
+        L, frame, cam, gs, radii, geom, img, None, out_color, out_depth, out_normal, moments, dist,
+        N.stream_of(means3D), "rasterize_gaussians" if dist is None else "rasterize_gaussians_dist")
+    return (num_rendered, out_color, radii, out_depth, out_normal, geom, binning, img) + \
+        ((moments,) if dist is not None else ())
 
 
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier,
@@ -347,7 +330,7 @@ def _backward(label, background, means3D, radii, colors, scales, rotations, scal
     frame = _frame(P, degree, M, W, H, tan_fovx, tan_fovy, scale_modifier, low_pass, False, debug)
     if nrm:  # the forward was rasterize_gaussians_aux
         frame.flags |= N.RR_FLAG_AUX_NORMAL
-    cam = N.RRCamera(_ptr(keep["bg"]), _ptr(keep["view"]), _ptr(keep["proj"]), _ptr(keep["campos"]))
+    _cam_keep, cam = driver.camera_block(keep["bg"], keep["view"], keep["proj"], keep["campos"])
     gs = N.RRGaussians(_ptr(keep["means3D"]), _ptr(keep["sh"]), _ptr(keep["colors"]), None,
                        _ptr(keep["scales"]), _ptr(keep["rotations"]), _ptr(keep["cov3D"]))
     # dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
@@ -358,25 +341,14 @@ def _backward(label, background, means3D, radii, colors, scales, rotations, scal
         res = res + (torch.empty((P, 3), **fopts),)
         grads.dL_dmeans2D_abs = _ptr(res[8])
     ws = torch.empty((L.rr_backward_workspace_bytes(P),), dtype=torch.uint8, device=device)
-    head = (ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs), _ptr(keep["radii"]), _ptr(geomBuffer),
-            _ptr(imageBuffer), _ptr(binningBuffer), int(R), _ptr(dpix))
-    tail = (_ptr(ws), ws.numel(), ctypes.byref(grads))
-    stream = N.stream_of(means3D)
+    cam_res = None
     if camera:
         if nrm or _present(dL_dout_moments):
             raise RuntimeError("camera gradients do not combine with dL_dout_normal / dL_dout_moments yet")
         cam_res = (torch.empty((4, 4), **fopts), torch.empty((4, 4), **fopts), torch.empty((3,), **fopts))
-        scratch = torch.empty((L.rr_camera_grad_scratch_bytes(P),), dtype=torch.uint8, device=device)
-        cg = N.RRCameraGrads(*[_ptr(t) for t in cam_res], _ptr(scratch), scratch.numel())
-        N.check(L.rr_backward_camera(*head, _ptr(ddepth), _ptr(dalpha), *tail, ctypes.byref(cg), stream), label)
-        return res + cam_res
-    # a colour-only backward stays on rr_backward (the reference's call); every other case is
-    # rr_backward_aux_dist, which with NULL maps is exactly each smaller entry point
-    fn, extra = L.rr_backward, ()
-    if aux:
-        fn, extra = L.rr_backward_aux_dist, (_ptr(ddepth), _ptr(dalpha), _ptr(dnormal), _ptr(dmoments), *dist)
-    N.check(fn(*head, *extra, *tail, stream), label)
-    return res
+    driver.backward(L, frame, cam, gs, keep["radii"], geomBuffer, imageBuffer, binningBuffer, R, dpix, ddepth, dalpha,
+                    dnormal, dmoments, dist, ws, grads, cam_res, N.stream_of(means3D), label)
+    return res + cam_res if camera else res
 
 
 def accumulated_alpha(imageBuffer, H, W):

@@ -9,6 +9,10 @@ backward kernel, which writes the six raw-parameter gradients straight into thei
 buffers and folds in the densification statistics — no SH concatenation, no autograd graph, no
 [P,3] means2D tensor.  The arithmetic is the same as the reference-API path (rain_amd.renderer /
 diff_gaussian_rasterization) on the activated tensors; tests/test_fused_gpu.py compares the two.
+
+This module holds RawFrame / NextFrame, the raw rr_grads packing, the argument checks and the autograd
+classes; the native call sequences (the one-call forward with its retry, the counted two-stage forward, the
+workspace registration, the choice of backward entry point) are rain_amd/_raster_driver.py's.
 """
 from __future__ import annotations
 
@@ -19,11 +23,11 @@ from dataclasses import dataclass
 import torch
 
 from . import _native as N
+from . import _raster_driver as driver
+# names tests, tools and bench.py use from this module; forward_params / forward_next look
+# _register_workspace up here at call time (tests replace it)
+from ._raster_driver import BinningCache, ptr as _p, register_workspace as _register_workspace
 from .diff_gaussian_rasterization import _C
-
-
-def _p(t):
-    return None if t is None or t.numel() == 0 else ctypes.c_void_p(t.data_ptr())
 
 
 @dataclass
@@ -48,22 +52,6 @@ class RawFrame:
     # the depth-moment maps [2,H,W] of a frame rendered with dist=(near, far), else None, and that pair
     moments: torch.Tensor | None = None
     dist: tuple | None = None
-
-
-class BinningCache:
-    """A grow-only binning buffer reused frame after frame (the training loop renders one frame,
-    runs its backward, then renders the next, all on one stream, so frame s+1's binning never
-    overwrites a list frame s's backward still reads).  With it the forward is one native call
-    (rr_forward): the device waits only for the pair-count read-back, not for a return to Python."""
-
-    def __init__(self, headroom: float = 1.25):
-        self.buf = None
-        self.headroom = headroom
-
-    def get(self, nbytes: int, dev) -> torch.Tensor:
-        if self.buf is None or self.buf.numel() < nbytes or self.buf.device != dev:
-            self.buf = torch.empty((int(nbytes * self.headroom) + 4096,), dtype=torch.uint8, device=dev)
-        return self.buf
 
 
 def forward(model, camera, bg: torch.Tensor, low_pass: float, scale_modifier: float = 1.0,
@@ -109,15 +97,13 @@ def forward_params(params, sh_degree: int, W: int, H: int, tanfovx: float, tanfo
         (N.RR_FLAG_ANTIALIAS if antialiasing else 0)
     frame = N.RRFrame(P, D, M, W, H, float(tanfovx), float(tanfovy), float(scale_modifier), float(low_pass), 0, 0,
                       flags)
-    keep = (bg.contiguous(), viewmatrix.contiguous(), projmatrix.contiguous(), campos.contiguous())
-    cam = N.RRCamera(*[_p(t) for t in keep])
+    keep, cam = driver.camera_block(bg, viewmatrix, projmatrix, campos)
     # kernel argument order: xyz, f_dc, opacity, scaling, rotation, f_rest
     params = tuple(t.detach() for t in (xyz, f_dc, params[3], params[4], params[5], f_rest))
     for t in params:
         if not t.is_contiguous() or t.dtype != torch.float32:
             raise RuntimeError("rain_amd.fused: parameters must be contiguous float32")
-    gs = N.RRGaussians(_p(params[0]), _p(params[1]), None, _p(params[2]), _p(params[3]), _p(params[4]), None,
-                       _p(params[5]))
+    gs = driver.raw_gaussians(*params)
     fo = dict(dtype=torch.float32, device=dev)
     u8 = dict(dtype=torch.uint8, device=dev)
     color = torch.empty((3, H, W), **fo)
@@ -126,7 +112,6 @@ def forward_params(params, sh_degree: int, W: int, H: int, tanfovx: float, tanfo
     geom = torch.empty((L.rr_geometry_bytes(P),), **u8)
     img = torch.empty((L.rr_image_bytes(W, H),), **u8)
     stream = N.stream_of(xyz)
-    nr, npairs = ctypes.c_int(0), ctypes.c_int(0)
     ws = _register_workspace(L, P, dev)
     # the aux normal frame goes through the two-stage calls (rr_forward renders no normal map)
     nmap = torch.empty((3, H, W), **fo) if normal else None
@@ -134,63 +119,23 @@ def forward_params(params, sh_degree: int, W: int, H: int, tanfovx: float, tanfo
         dist = (float(dist[0]), float(dist[1]))
     mom = torch.empty((2, H, W), **fo) if dist is not None else None
     if P > 0 and cache is not None and not normal and dist is None:
-        binning = cache.buf if cache.buf is not None and cache.buf.device == dev else torch.empty((0,), **u8)
-        need = ctypes.c_size_t(0)
-        rc = L.rr_forward(ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs), _p(radii), _p(geom), geom.numel(),
-                          _p(img), img.numel(), _p(binning), binning.numel(), ctypes.byref(nr), ctypes.byref(npairs),
-                          ctypes.byref(need), _p(color), _p(depth), stream)
-        if rc == N.RR_INCOMPLETE:  # the pairs outgrew the buffer: grow it and run stage 2
-            binning = cache.get(need.value, dev)
-            rc = L.rr_forward_render(ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs), _p(radii), _p(geom),
-                                     _p(img), _p(binning), binning.numel(), npairs.value, _p(color), _p(depth),
-                                     stream)
-        _check_render(L, rc, "fused forward")
-        st = RawFrame(frame, cam, gs, (keep, params), radii, geom, img, binning, nr.value, P, M, ws)
+        binning, num_rendered, _ = driver.render_one_call(L, frame, cam, gs, radii, geom, img, cache, color, depth,
+                                                          stream, "fused forward")
+        st = RawFrame(frame, cam, gs, (keep, params), radii, geom, img, binning, num_rendered, P, M, ws)
         return color, radii, depth, st
     if P > 0:
-        _check_render(L, L.rr_forward_geometry(ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs), _p(radii),
-                                               _p(geom), geom.numel(), _p(img), img.numel(), ctypes.byref(nr),
-                                               ctypes.byref(npairs), stream), "fused forward")
-    nbin = L.rr_binning_bytes(npairs.value, W, H) if npairs.value > 0 else 0
-    binning = cache.get(nbin, dev) if cache is not None and nbin > 0 else torch.empty((nbin,), **u8)
-    if P > 0 and dist is not None:
-        _check_render(L, L.rr_forward_render_dist(ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs),
-                                                  _p(radii), _p(geom), _p(img), _p(binning), binning.numel(),
-                                                  npairs.value, _p(color), _p(depth), _p(nmap), _p(mom), dist[0],
-                                                  dist[1], stream),
-                      "fused forward")
-    elif P > 0:
-        _check_render(L, L.rr_forward_render_aux(ctypes.byref(frame), ctypes.byref(cam), ctypes.byref(gs),
-                                                 _p(radii), _p(geom), _p(img), _p(binning), binning.numel(),
-                                                 npairs.value, _p(color), _p(depth), _p(nmap), stream),
-                      "fused forward")
+        binning, num_rendered = driver.render_counted(L, frame, cam, gs, radii, geom, img, cache, color, depth, nmap,
+                                                      mom, dist, stream, "fused forward")
     else:
+        binning, num_rendered = torch.empty((0,), **u8), 0
         color.copy_(bg.view(3, 1, 1).expand(3, H, W))
         depth.zero_()
         if normal:
             nmap.zero_()
         if mom is not None:
             mom.zero_()
-    st = RawFrame(frame, cam, gs, (keep, params), radii, geom, img, binning, nr.value, P, M, ws, nmap, mom, dist)
+    st = RawFrame(frame, cam, gs, (keep, params), radii, geom, img, binning, num_rendered, P, M, ws, nmap, mom, dist)
     return color, radii, depth, st
-
-
-def _register_workspace(L, P: int, dev) -> torch.Tensor | None:
-    """The backward's accumulator workspace, registered for the coming render to zero-fill
-    (rr_set_forward_workspace: the backward then skips its clear)."""
-    if P <= 0:
-        return None
-    ws = torch.empty((L.rr_backward_workspace_bytes(P),), dtype=torch.uint8, device=dev)
-    N.check(L.rr_set_forward_workspace(_p(ws), ws.numel()), "register workspace")
-    return ws
-
-
-def _check_render(L, rc: int, what: str):
-    """N.check, dropping a workspace registration a failed call left pending (it must not outlive
-    its buffer)."""
-    if rc not in (0, N.RR_INCOMPLETE):
-        L.rr_set_forward_workspace(None, 0)
-    N.check(rc, what)
 
 
 @dataclass
@@ -228,9 +173,7 @@ def prepare_next(model, camera, bg: torch.Tensor, low_pass: float, scale_modifie
     frame = N.RRFrame(P, int(model.active_sh_degree), M, W, H, math.tan(camera.FoVx * 0.5),
                       math.tan(camera.FoVy * 0.5), float(scale_modifier), float(low_pass), 0, 0,
                       N.RR_FLAG_RAW_PARAMS | _C.frame_flags() | (N.RR_FLAG_ANTIALIAS if antialiasing else 0))
-    keep = (bg.contiguous(), camera.world_view_transform.contiguous(), camera.full_proj_transform.contiguous(),
-            camera.camera_center.contiguous())
-    cam = N.RRCamera(*[_p(t) for t in keep])
+    keep, cam = driver.camera_block(bg, camera.world_view_transform, camera.full_proj_transform, camera.camera_center)
     radii = torch.empty((P,), dtype=torch.int32, device=dev)
     geom = torch.empty((L.rr_geometry_bytes(P),), dtype=torch.uint8, device=dev)
     return NextFrame(frame, cam, keep, radii, geom, P, M, W, H)
@@ -244,31 +187,16 @@ def forward_next(nxt: NextFrame, model, cache: BinningCache | None = None):
     P, W, H = nxt.P, nxt.W, nxt.H
     params = tuple(t.detach() for t in (model._xyz, model._features_dc, model._opacity, model._scaling,
                                         model._rotation, model._features_rest))
-    gs = N.RRGaussians(_p(params[0]), _p(params[1]), None, _p(params[2]), _p(params[3]), _p(params[4]), None,
-                       _p(params[5]))
-    fo = dict(dtype=torch.float32, device=dev)
-    u8 = dict(dtype=torch.uint8, device=dev)
-    color = torch.empty((3, H, W), **fo)
-    depth = torch.empty((1, H, W), **fo)
-    img = torch.empty((L.rr_image_bytes(W, H),), **u8)
-    stream = N.stream_of(nxt.geom)
-    nr, npairs = ctypes.c_int(0), ctypes.c_int(0)
-    need = ctypes.c_size_t(0)
+    gs = driver.raw_gaussians(*params)
+    color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
+    depth = torch.empty((1, H, W), dtype=torch.float32, device=dev)
+    img = torch.empty((L.rr_image_bytes(W, H),), dtype=torch.uint8, device=dev)
     ws = _register_workspace(L, P, dev)
-    binning = cache.buf if cache is not None and cache.buf is not None and cache.buf.device == dev \
-        else torch.empty((0,), **u8)
-    rc = L.rr_forward_from_geometry(ctypes.byref(nxt.frame), ctypes.byref(nxt.cam), _p(nxt.radii), _p(nxt.geom),
-                                    nxt.geom.numel(), _p(img), img.numel(), _p(binning), binning.numel(),
-                                    ctypes.byref(nr), ctypes.byref(npairs), ctypes.byref(need), _p(color), _p(depth),
-                                    stream)
-    if rc == N.RR_INCOMPLETE:  # the pairs outgrew the buffer: grow it and run the second stage
-        binning = cache.get(need.value, dev) if cache is not None else torch.empty((need.value,), **u8)
-        rc = L.rr_forward_render_geometry(ctypes.byref(nxt.frame), ctypes.byref(nxt.cam), _p(nxt.radii),
-                                          _p(nxt.geom), _p(img), _p(binning), binning.numel(), npairs.value,
-                                          _p(color), _p(depth), stream)
-    _check_render(L, rc, "fused forward (precomputed geometry)")
-    st = RawFrame(nxt.frame, nxt.cam, gs, (nxt.keep, params), nxt.radii, nxt.geom, img, binning, nr.value, P, nxt.M,
-                  ws)
+    binning, num_rendered, _ = driver.render_one_call(L, nxt.frame, nxt.cam, None, nxt.radii, nxt.geom, img, cache,
+                                                      color, depth, N.stream_of(nxt.geom),
+                                                      "fused forward (precomputed geometry)")
+    st = RawFrame(nxt.frame, nxt.cam, gs, (nxt.keep, params), nxt.radii, nxt.geom, img, binning, num_rendered, P,
+                  nxt.M, ws)
     return color, nxt.radii, depth, st
 
 
@@ -365,36 +293,17 @@ def backward(st: RawFrame, dL_dpix: torch.Tensor, grads: dict | None, stats: tup
                     _p(grads["scaling"]), _p(grads["rotation"]), _p(grads["f_rest"]), _p(acc), _p(den), _p(mr),
                     ctypes.pointer(adam) if adam is not None else None,
                     ctypes.pointer(next_frame.desc) if next_frame is not None else None, _p(dmeans2D_abs))
-    dev = dpix.device
-    frame = st.frame
-    if st.ws is not None:  # zero-filled by the forward render: the backward skips its clear
-        ws, st.ws = st.ws, None
-        frame = N.RRFrame.from_buffer_copy(st.frame)
-        frame.flags |= N.RR_FLAG_WORKSPACE_REGISTERED
-    else:
-        ws = torch.empty((L.rr_backward_workspace_bytes(st.P),), dtype=torch.uint8, device=dev)
-    if absgrad:  # a flag of this backward, on the frame copy
-        if frame is st.frame:
-            frame = N.RRFrame.from_buffer_copy(st.frame)
-        frame.flags |= N.RR_FLAG_ABSGRAD
-    head = (ctypes.byref(frame), ctypes.byref(st.cam), ctypes.byref(st.gs), _p(st.radii), _p(st.geom), _p(st.img),
-            _p(st.binning), st.num_rendered, _p(dpix) if dL_dpix is not None else None)
-    tail = (_p(ws), ws.numel(), ctypes.byref(out))
-    stream = N.stream_of(dpix)
-    if cam_grads is not None:
-        scratch = torch.empty((L.rr_camera_grad_scratch_bytes(st.P),), dtype=torch.uint8, device=dev)
-        cg = N.RRCameraGrads(_p(cam_grads[0]), _p(cam_grads[1]), _p(cam_grads[2]), _p(scratch), scratch.numel())
-        N.check(L.rr_backward_camera(*head, _p(maps[0]), _p(maps[1]), *tail, ctypes.byref(cg), stream),
-                "fused backward (camera)")
-        return
-    # a colour-only backward stays on rr_backward; every other case is rr_backward_aux_dist, which with NULL
-    # maps is exactly each smaller entry point: the library picks the kernel variants from the maps given
-    fn, extra, what = L.rr_backward, (), ""
-    if aux:
-        near, far = st.dist if maps[3] is not None else (0.0, 0.0)
-        fn, extra = L.rr_backward_aux_dist, (*[_p(m) for m in maps], near, far)
-        what = " (distortion)" if maps[3] is not None else " (normal)" if maps[2] is not None else " (depth)"
-    N.check(fn(*head, *extra, *tail, stream), "fused backward" + what)
+    # the workspace the forward's render zero-filled serves this backward (which then skips its clear); absgrad
+    # is a flag of this backward too: both go on a copy of the frame
+    ws, st.ws = st.ws, None
+    frame = driver.backward_frame(st.frame, ws is not None, N.RR_FLAG_ABSGRAD if absgrad else 0)
+    if ws is None:
+        ws = torch.empty((L.rr_backward_workspace_bytes(st.P),), dtype=torch.uint8, device=dpix.device)
+    what = " (camera)" if cam_grads is not None else " (distortion)" if maps[3] is not None else \
+        " (normal)" if maps[2] is not None else " (depth)" if aux else ""
+    driver.backward(L, frame, st.cam, st.gs, st.radii, st.geom, st.img, st.binning, st.num_rendered,
+                    dpix if dL_dpix is not None else None, maps[0], maps[1], maps[2], maps[3], st.dist, ws, out,
+                    cam_grads, N.stream_of(dpix), "fused backward" + what)
 
 
 def accumulated_alpha(st: RawFrame) -> torch.Tensor:

@@ -32,6 +32,10 @@ the single-GPU step on N views (tests/test_multirank_gpu.py).
 Parameters, Adam moments and statistics are current on their owner's rows only;
 `sync_replicas` all-gathers the row blocks where a full replica is read: densify / prune, opacity
 reset, checkpoints, evaluation, the end of training.
+
+This module holds the exchange and the row arithmetic; step 3's render (the one-call forward with its
+retry, the workspace registration, the binning buffer) and the row-offset rr_gaussians are
+rain_amd/_raster_driver.py's.
 """
 from __future__ import annotations
 
@@ -42,13 +46,11 @@ import torch
 import torch.distributed as dist
 
 from . import _native as N
+from . import _raster_driver as driver
+from ._raster_driver import ptr as _p
 
 REC_FLOATS = 10
 WIRE_BYTES = 40  # rr_preprocess_rows_views' wire record (the splat's 10 non-derived floats)
-
-
-def _p(t, byte_offset=0):
-    return None if t is None or t.numel() == 0 else ctypes.c_void_p(t.data_ptr() + byte_offset)
 
 
 def row_blocks(P: int, world: int):
@@ -67,6 +69,7 @@ class ShardedStep:
         self.ex = exchange
         self.rank, self.world = rank, world
         self._bufs = {}
+        self._binning = driver.BinningCache()
         self.rec_chunk_rows = rec_chunk_rows
 
     def chunk_rows(self, Q: int) -> int:
@@ -96,11 +99,8 @@ class ShardedStep:
     # ---- parameters of the owned rows --------------------------------------------------------
     @staticmethod
     def _row_params(model, lo):
-        M = 1 + model._features_rest.shape[1]
-        xyz, f_dc, f_rest = model._xyz, model._features_dc, model._features_rest
-        op, sc, rot = model._opacity, model._scaling, model._rotation
-        return N.RRGaussians(_p(xyz, 12 * lo), _p(f_dc, 12 * lo), None, _p(op, 4 * lo), _p(sc, 12 * lo),
-                             _p(rot, 16 * lo), None, _p(f_rest, 12 * (M - 1) * lo) if M > 1 else None), M
+        return driver.raw_gaussians(model._xyz, model._features_dc, model._opacity, model._scaling, model._rotation,
+                                    model._features_rest, lo), 1 + model._features_rest.shape[1]
 
     def _frame(self, model, P, cam, low_pass, flags):
         D = model.active_sh_degree
@@ -136,39 +136,25 @@ class ShardedStep:
         # 3. render this rank's view from the geometry, loss, blend backward -> records
         cam = cams[self.rank]
         fr = self._frame(model, P_pad, cam, low_pass, flags)
-        k = keep[self.rank]
-        rc = N.RRCamera(*[_p(t) for t in k])
+        _k, rc = driver.camera_block(*keep[self.rank])
         H, W = int(cam.image_height), int(cam.image_width)
         img = torch.empty((int(L.rr_image_bytes(W, H)),), dtype=u8, device=dev)
         color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
         depth = torch.empty((1, H, W), dtype=torch.float32, device=dev)
-        binning = self._bufs.get("binning")
-        if binning is None or binning.device != dev:
-            binning = torch.empty((0,), dtype=u8, device=dev)
-        nr, npairs, need = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_size_t(0)
         # the blend backward's accumulators, zero-filled by this render's blend launch
         # (rr_set_forward_workspace): the backward then skips its 64-MB clear
-        ws = self._buf("ws", int(L.rr_backward_workspace_bytes(P_pad)), u8, dev)
-        N.check(L.rr_set_forward_workspace(_p(ws), ws.numel()), "register workspace")
-        r = L.rr_forward_from_geometry(ctypes.byref(fr), ctypes.byref(rc), _p(radii), _p(geom), geom.numel(), _p(img),
-                                       img.numel(), _p(binning), binning.numel(), ctypes.byref(nr),
-                                       ctypes.byref(npairs), ctypes.byref(need), _p(color), _p(depth), stream)
-        if r == N.RR_INCOMPLETE:
-            binning = self._bufs["binning"] = torch.empty((int(need.value * 1.25) + 4096,), dtype=u8, device=dev)
-            r = L.rr_forward_render_geometry(ctypes.byref(fr), ctypes.byref(rc), _p(radii), _p(geom), _p(img),
-                                             _p(binning), binning.numel(), npairs.value, _p(color), _p(depth), stream)
-        if r not in (0, N.RR_INCOMPLETE):
-            L.rr_set_forward_workspace(None, 0)  # a failed render must not leave the registration behind
-        N.check(r, "sharded forward")
-        self.last = dict(num_rendered=nr.value, num_pairs=npairs.value, P_pad=P_pad, Q=Q)
+        ws = driver.register_workspace(L, P_pad, dev,
+                                       self._buf("ws", int(L.rr_backward_workspace_bytes(P_pad)), u8, dev))
+        binning, num_rendered, num_pairs = driver.render_one_call(L, fr, rc, None, radii, geom, img, self._binning,
+                                                                  color, depth, stream, "sharded forward")
+        self.last = dict(num_rendered=num_rendered, num_pairs=num_pairs, P_pad=P_pad, Q=Q)
         dimg, loss = loss_fn(color)
         dimg = dimg.contiguous()
         recs = self._buf("recs", P_pad * REC_FLOATS, torch.float32, dev)
         CR = self.chunk_rows(Q)
-        frb = N.RRFrame.from_buffer_copy(fr)
-        frb.flags |= N.RR_FLAG_WORKSPACE_REGISTERED
+        frb = driver.backward_frame(fr, True)
         N.check(L.rr_backward_records(ctypes.byref(frb), ctypes.byref(rc), _p(radii), _p(geom), _p(img), _p(binning),
-                                      nr.value, _p(dimg), _p(ws), ws.numel(), Q, CR, _p(recs), stream),
+                                      num_rendered, _p(dimg), _p(ws), ws.numel(), Q, CR, _p(recs), stream),
                 "sharded backward")
 
         self.exchange_and_own(model, cams, keep, recs, low_pass, adam, stats)
@@ -195,8 +181,8 @@ class ShardedStep:
             c += w * n
         chunk = (c + 255) // 256 * 256
         send = self._buf("g_send", Nw * chunk, torch.uint8, dev)
-        keep = [(bg.contiguous(), cam.world_view_transform.contiguous(), cam.full_proj_transform.contiguous(),
-                 cam.camera_center.contiguous()) for cam in cams]
+        keep = [driver.camera_block(bg, cam.world_view_transform, cam.full_proj_transform, cam.camera_center)[0]
+                for cam in cams]
         # every view in one launch (rr_preprocess_rows_views): view v's chunk at v * chunk
         views = (N.RRView * Nw)()
         for v, (cam, k) in enumerate(zip(cams, keep)):
