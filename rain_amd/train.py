@@ -29,7 +29,8 @@ import torch
 import torch.distributed as dist
 
 from .gaussian_model import GaussianModel, OptimizationParams, low_pass_schedule
-from .loss import fused_distortion_loss, fused_geometry_loss, fused_l1_ssim_loss
+from .loss import (distortion_loss_forward_backward, fused_distortion_loss, fused_geometry_loss, fused_l1_ssim_loss,
+                   geometry_loss_forward_backward, l1_ssim_forward_backward)
 from .optim import sharded_adam_step
 from .renderer import PipelineParams, render
 
@@ -175,6 +176,103 @@ class StepInfo:
     densified: bool = False
 
 
+@dataclass(frozen=True)
+class StepOptions:
+    """The opt-in modes of a training step, as resolve_options read them from the parameter objects."""
+    mcmc: bool                     # densify_strategy "mcmc" (rain_amd/mcmc.py)
+    absgrad: bool                  # densify_absgrad (AbsGS; RR_FLAG_ABSGRAD)
+    antialiasing: bool             # pipe.antialiasing (opacity compensation of the 2D dilation, RR_FLAG_ANTIALIAS)
+    lambda_normal: float           # weight of the depth-normal consistency term, >= 0,
+    lambda_normal_from_iter: int   # applied from this iteration on
+    lambda_dist: float             # weight of the depth-distortion term, >= 0,
+    lambda_dist_from_iter: int     # applied from this iteration on
+    dist_range: tuple              # (dist_near, dist_far) of the distortion term's NDC depth
+    prune_iterations: tuple        # iterations that end with an importance prune; empty without a positive fraction
+
+    def normal_weight(self, it: int) -> float:
+        return self.lambda_normal if it >= self.lambda_normal_from_iter else 0.0
+
+    def dist_weight(self, it: int) -> float:
+        return self.lambda_dist if it >= self.lambda_dist_from_iter else 0.0
+
+    def prune_at(self, it: int) -> bool:
+        return it in self.prune_iterations
+
+
+def resolve_options(opt, pipe, sharded: bool) -> StepOptions:
+    """The opt-in modes of OptimizationParams `opt` and PipelineParams `pipe` for a step that is `sharded`
+    (Gaussian-sharded or multi-rank) or not.  Every optional field is read here and nowhere else; a parameter
+    object from before a field existed lacks it, which means the mode is off.  Raises ValueError for what the
+    step cannot do: each of these modes needs the single-GPU step, and some do not combine."""
+    def get(name, default):
+        return getattr(opt, name, default)
+
+    lam_n = float(get("lambda_normal", 0.0) or 0.0)
+    lam_t = float(get("lambda_dist", 0.0) or 0.0)
+    prune_its = tuple(get("importance_prune_iterations", ()) or ())
+    antialiasing = bool(getattr(pipe, "antialiasing", False))
+    absgrad = bool(get("densify_absgrad", False))
+    strategy = get("densify_strategy", "default")
+    if lam_n > 0.0 and sharded:
+        raise ValueError("lambda_normal > 0 needs the single-GPU step: the Gaussian-sharded / multi-rank steps "
+                         "have no normal-map backward (k_gauss_bwd_views has no normal variant); train on one "
+                         "GPU or set lambda_normal = 0")
+    if lam_t > 0.0 and sharded:
+        raise ValueError("lambda_dist > 0 needs the single-GPU step: the Gaussian-sharded / multi-rank steps "
+                         "have no depth-moment backward (k_gauss_bwd_views has no depth variant); train on one "
+                         "GPU or set lambda_dist = 0")
+    if prune_its and sharded:
+        raise ValueError("importance_prune_iterations needs the single-GPU step: the Gaussian-sharded / "
+                         "multi-rank steps have no contribution statistics; train on one GPU or leave it empty")
+    if antialiasing and sharded:
+        raise ValueError("pipe.antialiasing needs the single-GPU step: the Gaussian-sharded / multi-rank steps "
+                         "have no opacity compensation (rr_preprocess_rows and k_gauss_bwd_views refuse "
+                         "RR_FLAG_ANTIALIAS); train on one GPU or set antialiasing = False")
+    if absgrad:  # refused where the statistic cannot be formed yet or is not used
+        if sharded:
+            raise ValueError("densify_absgrad needs the single-GPU step: the Gaussian-sharded / multi-rank steps "
+                             "carry no absolute sums (rr_backward_records and rr_gauss_backward_views refuse "
+                             "RR_FLAG_ABSGRAD); train on one GPU or set densify_absgrad = False")
+        if strategy == "mcmc":
+            raise ValueError("densify_absgrad does not combine with densify_strategy 'mcmc': that strategy uses no "
+                             "gradient statistic; set densify_absgrad = False")
+        if lam_n != 0.0 or lam_t != 0.0:
+            raise ValueError("densify_absgrad does not combine with lambda_normal / lambda_dist yet (follow-up: "
+                             "absolute sums in the depth / normal / moment backward variants); set both to 0")
+    if strategy != "default":  # cap_max is read only under "mcmc"
+        if strategy != "mcmc":
+            raise ValueError(f"densify_strategy must be 'default' or 'mcmc', got {strategy!r}")
+        if int(get("cap_max", 0) or 0) <= 0:
+            raise ValueError("densify_strategy 'mcmc' needs cap_max > 0: the number of Gaussians the set grows to")
+        if sharded:
+            raise ValueError("densify_strategy 'mcmc' needs the single-GPU step: the Gaussian-sharded / multi-rank "
+                             "steps have no relocation or noise step; train on one GPU or use the default strategy")
+        if lam_n != 0.0 or lam_t != 0.0:
+            raise ValueError("densify_strategy 'mcmc' does not combine with lambda_normal / lambda_dist yet: its step "
+                             "renders the colour image only; set both to 0")
+        if prune_its:
+            raise ValueError("densify_strategy 'mcmc' does not combine with importance_prune_iterations yet: the "
+                             "set is bounded by cap_max; leave it empty")
+    if float(get("importance_prune_fraction", 0.0) or 0.0) <= 0.0:
+        prune_its = ()
+    return StepOptions(mcmc=strategy == "mcmc", absgrad=absgrad, antialiasing=antialiasing,
+                       lambda_normal=max(lam_n, 0.0), lambda_normal_from_iter=int(get("lambda_normal_from_iter", 0)),
+                       lambda_dist=max(lam_t, 0.0), lambda_dist_from_iter=int(get("lambda_dist_from_iter", 0)),
+                       dist_range=(float(get("dist_near", 0.2)), float(get("dist_far", 100.0))),
+                       prune_iterations=prune_its)
+
+
+@dataclass
+class PendingFrame:
+    """What step s decided for step s + 1 under Trainer.fuse_next, and the frame its backward preprocessed."""
+    iteration: int
+    view: int
+    camera: object
+    low_pass: float
+    frame: object             # rain_amd.fused.NextFrame
+    signature: tuple = ()     # Trainer._params_signature() of the parameters the frame was computed from
+
+
 class Trainer:
     def __init__(self, gaussians: GaussianModel, cameras, gt_images, opt: OptimizationParams | None = None,
                  pipe: PipelineParams | None = None, cfg: TrainConfig | None = None, scene_extent: float = 1.0,
@@ -207,9 +305,9 @@ class Trainer:
         # Fused step (rain_amd.fused): getters + their backward inside the rasterizer, gradients
         # written straight into the flat buffer, densification statistics folded into the backward
         # kernel, no autograd graph.  Needs the default loss and the SH / scale-rotation path.
-        plain_pipe = not (self.pipe.convert_SHs_python or self.pipe.compute_cov3D_python)
-        auto = dev.type == "cuda" and loss_fn is None and plain_pipe
-        self.fused = auto if fused is None else bool(fused)
+        fusable = (dev.type == "cuda" and loss_fn is None
+                   and not (self.pipe.convert_SHs_python or self.pipe.compute_cov3D_python))
+        self.fused = fusable if fused is None else bool(fused)
         self._bin_cache = None
         self.reuse_binning = True  # fused step: one native forward call over a reused binning buffer
         # fused step, single GPU: the backward of step s also preprocesses step s+1's frame on the
@@ -223,7 +321,7 @@ class Trainer:
         # (replaced tensors, or in-place edits such as a manual reset or a checkpoint restore: the
         # tensors' version counters), and step s+1 then preprocesses normally.
         self.fuse_next = True
-        self._pending = None  # (iteration, view index, camera, low_pass, NextFrame or None, params signature)
+        self._pending: PendingFrame | None = None
         self._shard = None
         # the fused step on N > 1 ranks (or a forced exchange): Gaussian-sharded, view-parallel
         # (rain_amd/sharded.py); the autograd step keeps the replicated gradient exchange
@@ -232,170 +330,74 @@ class Trainer:
             from .sharded import ShardedStep
 
             self._owner = ShardedStep(self.exchange, self.rank, self.world)
-        if self.fused and not (dev.type == "cuda" and loss_fn is None and plain_pipe):
+        if self.fused and not fusable:
             raise ValueError("fused step needs a HIP device, the default loss and the default pipeline")
-        self._geometry_weight(0)  # a non-zero lambda_normal on the sharded paths is refused here already
-        self._distortion_weight(0)  # and so is a non-zero lambda_dist
-        self._importance_prune_now(0)  # and importance pruning
-        self._antialiasing()  # and pipe.antialiasing
-        # and densify_absgrad (also refused with the geometry terms and under "mcmc"); decided once, here
-        self._absgrad_on = self._absgrad()
+        # Refuses what the (sharded) step cannot do at construction already.  step() resolves again: `opt`,
+        # `pipe` and `sharded` may be edited between steps, and an edit takes effect, or is refused, at the next.
+        self.options = resolve_options(self.opt, self.pipe, self.sharded)
         self.noise_gen = None
-        if self._mcmc():  # (checks the options it does not combine with)
+        if self.options.mcmc:
             self.noise_gen = torch.Generator(device=dev).manual_seed(self.cfg.seed + 54321)
 
-    def _antialiasing(self) -> bool:
-        """PipelineParams.antialiasing (the opacity compensation of the 2D dilation, RR_FLAG_ANTIALIAS), which
-        the single-GPU steps pass to every frame they render; the sharded steps refuse it."""
-        aa = bool(getattr(self.pipe, "antialiasing", False))
-        if aa and self.sharded:
-            raise ValueError("pipe.antialiasing needs the single-GPU step: the Gaussian-sharded / multi-rank steps "
-                             "have no opacity compensation (rr_preprocess_rows and k_gauss_bwd_views refuse "
-                             "RR_FLAG_ANTIALIAS); train on one GPU or set antialiasing = False")
-        return aa
-
-    def _absgrad(self) -> bool:
-        """OptimizationParams.densify_absgrad (AbsGS; RR_FLAG_ABSGRAD): the single-GPU steps feed
-        xyz_gradient_accum with the norm of the absolute per-pixel mean-gradient sums.  Refused where the
-        statistic cannot be formed yet or is not used."""
-        opt = self.opt
-        if not bool(getattr(opt, "densify_absgrad", False)):
-            return False
-        if self.sharded:
-            raise ValueError("densify_absgrad needs the single-GPU step: the Gaussian-sharded / multi-rank steps "
-                             "carry no absolute sums (rr_backward_records and rr_gauss_backward_views refuse "
-                             "RR_FLAG_ABSGRAD); train on one GPU or set densify_absgrad = False")
-        if getattr(opt, "densify_strategy", "default") == "mcmc":
-            raise ValueError("densify_absgrad does not combine with densify_strategy 'mcmc': that strategy uses no "
-                             "gradient statistic; set densify_absgrad = False")
-        if any(float(getattr(opt, k, 0.0) or 0.0) != 0.0 for k in ("lambda_normal", "lambda_dist")):
-            raise ValueError("densify_absgrad does not combine with lambda_normal / lambda_dist yet (follow-up: "
-                             "absolute sums in the depth / normal / moment backward variants); set both to 0")
-        return True
-
-    def _mcmc(self) -> bool:
-        """Whether OptimizationParams.densify_strategy selects the MCMC step (rain_amd/mcmc.py); refuses an
-        unknown strategy, a missing cap and the options that step does not carry yet."""
-        opt = self.opt
-        strategy = getattr(opt, "densify_strategy", "default")
-        if strategy == "default":
-            return False
-        if strategy != "mcmc":
-            raise ValueError(f"densify_strategy must be 'default' or 'mcmc', got {strategy!r}")
-        if int(getattr(opt, "cap_max", 0) or 0) <= 0:
-            raise ValueError("densify_strategy 'mcmc' needs cap_max > 0: the number of Gaussians the set grows to")
-        if self.sharded:
-            raise ValueError("densify_strategy 'mcmc' needs the single-GPU step: the Gaussian-sharded / multi-rank "
-                             "steps have no relocation or noise step; train on one GPU or use the default strategy")
-        if any(float(getattr(opt, k, 0.0) or 0.0) != 0.0 for k in ("lambda_normal", "lambda_dist")):
-            raise ValueError("densify_strategy 'mcmc' does not combine with lambda_normal / lambda_dist yet: its step "
-                             "renders the colour image only; set both to 0")
-        if tuple(getattr(opt, "importance_prune_iterations", ()) or ()):
-            raise ValueError("densify_strategy 'mcmc' does not combine with importance_prune_iterations yet: the "
-                             "set is bounded by cap_max; leave it empty")
-        return True
+    def _sh_ramp(self, iteration) -> bool:
+        """Whether `iteration` raises the active SH degree, while it is below the maximum (train.py:79-85)."""
+        if self.cfg.ours or self.cfg.ours_new:
+            return iteration >= 5000 and iteration % 1000 == 0
+        return iteration % 1000 == 0
 
     def _low_pass_and_view(self, iteration):
+        """The start of `iteration`: learning rate, SH ramp, this rank's view of the next group and the
+        low-pass the schedule gives it, as (view index, camera, low_pass).  The step that renders it stores
+        that value in `self.low_pass`, which the schedule holds between its updates."""
         g, opt, cfg = self.g, self.opt, self.cfg
         if cfg.ours_new:  # train.py:73-75: the schedule starts after the warm-up
             if iteration >= cfg.warmup_iter:
                 g.update_learning_rate(iteration - cfg.warmup_iter)
         else:
             g.update_learning_rate(iteration)
-        if cfg.ours or cfg.ours_new:
-            if iteration >= 5000 and iteration % 1000 == 0:
-                g.oneupSHdegree()
-        elif iteration % 1000 == 0:
+        if self._sh_ramp(iteration):
             g.oneupSHdegree()
         views = self.sampler.next_group()
         self._views = views
         vidx = views[self.rank]
-        cam = self.cams[vidx]
-        if cfg.c2f:
-            if iteration == 1 or (iteration % cfg.c2f_every_step == 0 and iteration < opt.densify_until_iter):
-                # one value per step on every rank: the schedule reads the image size of the step's
-                # FIRST view (views[0], the one a single process would render first), so ranks whose
-                # own views differ in size still blur every Gaussian alike
-                c0 = self.cams[views[0]]
-                self.low_pass = low_pass_schedule(c0.image_height, c0.image_width, g.get_xyz.shape[0],
-                                                  cfg.c2f_max_lowpass)
-        else:
-            self.low_pass = 0.3
-        return vidx, cam
-
-    def _sh_steps_up(self, iteration) -> bool:
-        """Whether _low_pass_and_view(iteration) raises the active SH degree (train.py:79-85)."""
-        g, cfg = self.g, self.cfg
-        if g.active_sh_degree >= g.max_sh_degree:
-            return False
-        if cfg.ours or cfg.ours_new:
-            return iteration >= 5000 and iteration % 1000 == 0
-        return iteration % 1000 == 0
+        low_pass = self.low_pass if cfg.c2f else 0.3
+        if cfg.c2f and (iteration == 1 or (iteration % cfg.c2f_every_step == 0
+                                           and iteration < opt.densify_until_iter)):
+            # one value per step on every rank: the schedule reads the image size of the step's
+            # FIRST view (views[0], the one a single process would render first), so ranks whose
+            # own views differ in size still blur every Gaussian alike
+            c0 = self.cams[views[0]]
+            low_pass = low_pass_schedule(c0.image_height, c0.image_width, g.get_xyz.shape[0], cfg.c2f_max_lowpass)
+        return vidx, self.cams[vidx], low_pass
 
     def _events(self, iteration):
-        """(densify/prune now, opacity reset now) — train.py:136-143."""
+        """(densify now, opacity reset now) — train.py:136-143.  Under densify_strategy "mcmc" the first is
+        its relocate-and-grow event, and no reset runs."""
         opt, cfg = self.opt, self.cfg
         if iteration >= opt.densify_until_iter:
             return False, False
-        densify = cfg.densify and iteration > opt.densify_from_iter and iteration % opt.densification_interval == 0
+        densify = bool(cfg.densify and iteration > opt.densify_from_iter
+                       and iteration % opt.densification_interval == 0)
         reset = iteration % opt.opacity_reset_interval == 0 or (cfg.white_background and
                                                                  iteration == opt.densify_from_iter)
         return densify, reset
 
     def _densify_and_adam(self, iteration, adam_done=False):
-        g, opt, cfg = self.g, self.opt, self.cfg
-        densified = False
-        if iteration < opt.densify_until_iter:
-            if cfg.densify and iteration > opt.densify_from_iter and iteration % opt.densification_interval == 0:
-                size_threshold = 20 if iteration > opt.opacity_reset_interval else None
-                abe_split = iteration <= cfg.warmup_iter
-                g.densify_and_prune(opt.densify_grad_threshold, 0.005, self.extent, size_threshold, N=2,
-                                    abe_split=abe_split, generator=self.densify_gen)
-                densified = True
-            if iteration % opt.opacity_reset_interval == 0 or (cfg.white_background and
-                                                               iteration == opt.densify_from_iter):
-                g.reset_opacity()
+        g, opt = self.g, self.opt
+        densify_now, reset_now = self._events(iteration)
+        if densify_now:
+            size_threshold = 20 if iteration > opt.opacity_reset_interval else None
+            abe_split = iteration <= self.cfg.warmup_iter
+            g.densify_and_prune(opt.densify_grad_threshold, 0.005, self.extent, size_threshold, N=2,
+                                abe_split=abe_split, generator=self.densify_gen)
+        if reset_now:
+            g.reset_opacity()
         if iteration < opt.iterations and not adam_done:
             # after densify_and_prune the parameters are new tensors with grad None, so this step
             # skips them, exactly as the reference's optimizer.step() does (train.py:145-147)
             g.optimizer.step()
             g.optimizer.zero_grad(set_to_none=True)
-        return densified
-
-    def _geometry_weight(self, iteration: int) -> float:
-        """The weight of the depth-normal consistency term at `iteration`: OptimizationParams.lambda_normal
-        from lambda_normal_from_iter on, else 0 (today's step, untouched)."""
-        lam = float(getattr(self.opt, "lambda_normal", 0.0) or 0.0)
-        if lam <= 0.0:
-            return 0.0
-        if self.sharded:
-            raise ValueError("lambda_normal > 0 needs the single-GPU step: the Gaussian-sharded / multi-rank steps "
-                             "have no normal-map backward (k_gauss_bwd_views has no normal variant); train on one "
-                             "GPU or set lambda_normal = 0")
-        return lam if iteration >= int(getattr(self.opt, "lambda_normal_from_iter", 0)) else 0.0
-
-    def _distortion_weight(self, iteration: int) -> float:
-        """The weight of the depth-distortion term at `iteration`: OptimizationParams.lambda_dist from
-        lambda_dist_from_iter on, else 0 (today's step, untouched)."""
-        lam = float(getattr(self.opt, "lambda_dist", 0.0) or 0.0)
-        if lam <= 0.0:
-            return 0.0
-        if self.sharded:
-            raise ValueError("lambda_dist > 0 needs the single-GPU step: the Gaussian-sharded / multi-rank steps "
-                             "have no depth-moment backward (k_gauss_bwd_views has no depth variant); train on one "
-                             "GPU or set lambda_dist = 0")
-        return lam if iteration >= int(getattr(self.opt, "lambda_dist_from_iter", 0)) else 0.0
-
-    def _importance_prune_now(self, iteration: int) -> bool:
-        """Whether this iteration ends with an importance prune (OptimizationParams.importance_prune_iterations,
-        with a positive importance_prune_fraction); the defaults never do."""
-        its = tuple(getattr(self.opt, "importance_prune_iterations", ()) or ())
-        if not its:
-            return False
-        if self.sharded:
-            raise ValueError("importance_prune_iterations needs the single-GPU step: the Gaussian-sharded / "
-                             "multi-rank steps have no contribution statistics; train on one GPU or leave it empty")
-        return iteration in its and float(getattr(self.opt, "importance_prune_fraction", 0.0) or 0.0) > 0.0
+        return densify_now
 
     def _importance_prune(self):
         """Score every Gaussian over the training cameras and remove the lowest-scoring fraction.  The
@@ -408,15 +410,35 @@ class Trainer:
             scores = importance.importance_scores(stats, self.g, kind=opt.importance_prune_kind)
             self.g.prune_by_importance(scores, fraction=float(opt.importance_prune_fraction))
 
-    def _dist_range(self):
-        return float(getattr(self.opt, "dist_near", 0.2)), float(getattr(self.opt, "dist_far", 100.0))
-
     def step(self, iteration: int, sync_loss: bool = False) -> StepInfo:
-        if self._mcmc():
+        self.options = resolve_options(self.opt, self.pipe, self.sharded)
+        if self.options.mcmc:
             return self._step_mcmc(iteration, sync_loss)
-        if self.fused:
-            return self._step_fused(iteration, sync_loss)
-        return self._step_autograd(iteration, sync_loss)
+        if not self.fused:
+            return self._step_autograd(iteration, sync_loss)
+        if self._owner is not None:
+            return self._step_owner(iteration, sync_loss)
+        return self._step_fused(iteration, sync_loss)
+
+    def _info(self, loss, sync_loss, view, densified) -> StepInfo:
+        return StepInfo(loss=float(loss.item()) if sync_loss else None, num_gaussians=self.g.get_xyz.shape[0],
+                        view=view, low_pass=self.low_pass, densified=densified)
+
+    def _bind_grads(self) -> dict:
+        """The parameters' gradients as views into the flat buffer, for the fused backward, which overwrites
+        every one of them."""
+        g = self.g
+        g.bind_flat_grad(zero=False)
+        return dict(xyz=g._xyz.grad, f_dc=g._features_dc.grad, f_rest=g._features_rest.grad, opacity=g._opacity.grad,
+                    scaling=g._scaling.grad, rotation=g._rotation.grad)
+
+    def _binning(self):
+        """The binning buffer the fused forwards reuse from step to step (None with reuse_binning off)."""
+        if self._bin_cache is None:
+            from . import fused
+
+            self._bin_cache = fused.BinningCache()
+        return self._bin_cache if self.reuse_binning else None
 
     def _step_owner(self, iteration: int, sync_loss: bool) -> StepInfo:
         """The fused step on the Gaussian-sharded ranks (rain_amd/sharded.py): one view per rank, Adam
@@ -425,14 +447,13 @@ class Trainer:
         densify iteration the reference's optimizer.step() finds only replaced parameters (no step),
         on a reset-only iteration it steps every group but the replaced opacity."""
         from .diff_gaussian_rasterization import _C
-        from .loss import l1_ssim_forward_backward
 
         g, opt = self.g, self.opt
         if not hasattr(g.optimizer, "fused_step"):  # before any collective of the step starts
             raise ValueError("the Gaussian-sharded fused step applies Adam inside its owner kernel: the model's "
                              "optimizer must be rain_amd.optim.FusedAdam (GaussianModel.training_setup builds one); "
                              "use Trainer(fused=False) for another optimizer")
-        vidx, _cam = self._low_pass_and_view(iteration)
+        vidx, _cam, self.low_pass = self._low_pass_and_view(iteration)
         cams = [self.cams[v] for v in self._views]
         densify_phase = iteration < opt.densify_until_iter
         densify_now, reset_now = self._events(iteration)
@@ -454,8 +475,7 @@ class Trainer:
             if densify_now or reset_now:
                 self._owner.sync_replicas(g)
                 densified = self._densify_and_adam(iteration, adam_done=True)
-        return StepInfo(loss=float(loss.item()) if sync_loss else None, num_gaussians=g.get_xyz.shape[0],
-                        view=vidx, low_pass=self.low_pass, densified=densified)
+        return self._info(loss, sync_loss, vidx, densified)
 
     def sync_state(self):
         """Make every rank's GaussianModel a full, current replica (parameters, Adam moments,
@@ -474,73 +494,57 @@ class Trainer:
         return tuple((p.data_ptr(), p._version) for p in self.g.params())
 
     def _step_fused(self, iteration: int, sync_loss: bool) -> StepInfo:
+        """The fused step on one GPU (rain_amd.fused); the Gaussian-sharded ranks run _step_owner instead."""
         from . import fused
-        from .loss import distortion_loss_forward_backward, geometry_loss_forward_backward, l1_ssim_forward_backward
 
-        lam_n = self._geometry_weight(iteration)  # refuses the sharded steps when the weight is set
-        lam_t = self._distortion_weight(iteration)  # likewise
-        prune_now = self._importance_prune_now(iteration)  # likewise
-        if self._owner is not None:
-            return self._step_owner(iteration, sync_loss)
-
-        if self._bin_cache is None:
-            self._bin_cache = fused.BinningCache()
-        g, opt = self.g, self.opt
+        g, opt, o = self.g, self.opt, self.options
+        lam_n, lam_t = o.normal_weight(iteration), o.dist_weight(iteration)
+        prune_now = o.prune_at(iteration)
+        cache = self._binning()
         pend, self._pending = self._pending, None
-        if pend is not None and pend[0] == iteration:  # decided (and maybe preprocessed) by step s-1
-            _it, vidx, cam, self.low_pass, nxt, sig = pend
-            if nxt is not None and (nxt.P != g.get_xyz.shape[0] or nxt.frame.D != g.active_sh_degree
-                                    or sig != self._params_signature()):
-                nxt = None  # the parameters changed since step s-1's backward preprocessed this frame
-            if lam_n or lam_t:
-                nxt = None  # a frame with the aux normal map or the moment maps runs its own preprocess
+        if pend is not None and pend.iteration == iteration:  # decided and preprocessed by step s-1
+            vidx, cam, self.low_pass, nxt = pend.view, pend.camera, pend.low_pass, pend.frame
+            # not if the parameters changed since step s-1's backward preprocessed this frame, and a frame with
+            # the aux normal map or the moment maps runs its own preprocess
+            if (nxt.P != g.get_xyz.shape[0] or nxt.frame.D != g.active_sh_degree
+                    or pend.signature != self._params_signature() or lam_n or lam_t):
+                nxt = None
         else:
-            vidx, cam = self._low_pass_and_view(iteration)
+            vidx, cam, self.low_pass = self._low_pass_and_view(iteration)
             nxt = None
         densify_phase = iteration < opt.densify_until_iter
         densify_now, reset_now = self._events(iteration)
-        # Single GPU, and no densify/prune or opacity reset this iteration (they replace parameter
-        # tensors before the reference's optimizer.step()): the Adam step runs inside the backward
-        # kernel and the gradients never exist in HBM.
-        fuse_adam = (not self.sharded and iteration < opt.iterations and not densify_now and not reset_now
+        # No densify/prune or opacity reset this iteration (they replace parameter tensors before the
+        # reference's optimizer.step()): the Adam step runs inside the backward kernel and the gradients
+        # never exist in HBM.
+        fuse_adam = (iteration < opt.iterations and not densify_now and not reset_now
                      and hasattr(g.optimizer, "fused_step"))
-        if self.sharded:
-            g.pack_flat_state(self.world)
-        flat = None if fuse_adam else g.bind_flat_grad(zero=False, pad_to=self.world)  # backward overwrites all
         # Everything the backward needs from Python is prepared BEFORE the forward: the forward's one
         # host wait (the pair-count read-back, rasterizer_impl.cu:273) returns when the device is at
         # this frame's depth sort, and from there the host must enqueue the binning, the blends, the
         # loss and the backward faster than the device runs them (~0.45 ms of kernels); the Adam
         # block (step counts, bias corrections) does not depend on the frame.
         adam = g.optimizer.fused_step(g) if fuse_adam else None
-        grads = None if fuse_adam else dict(
-            xyz=g._xyz.grad, f_dc=g._features_dc.grad, f_rest=g._features_rest.grad, opacity=g._opacity.grad,
-            scaling=g._scaling.grad, rotation=g._rotation.grad)
-        # densification statistics accumulate per rank; ranks merge them only when densify consumes
-        # them (_finish)
+        grads = None if fuse_adam else self._bind_grads()
         stats = (g.xyz_gradient_accum, g.denom, g.max_radii2D) if densify_phase else None
         gt = self.gt[vidx]
         # the next step's frame, preprocessed by this step's backward: only when this step's Adam runs
-        # inside that backward (no densify / reset replacing parameters) and the SH degree stays
+        # inside that backward (no densify / reset replacing parameters), the SH degree stays and neither
+        # step renders the aux maps of the geometry terms
         next_frame = None
-        if (fuse_adam and self.fuse_next and not self.sharded and iteration + 1 < opt.iterations and not prune_now
-                and not self._sh_steps_up(iteration + 1) and not lam_n and not self._geometry_weight(iteration + 1)
-                and not lam_t and not self._distortion_weight(iteration + 1)):
-            low_pass_now = self.low_pass
-            vidx1, cam1 = self._low_pass_and_view(iteration + 1)
-            next_frame = fused.prepare_next(g, cam1, self.background, self.low_pass,
-                                            antialiasing=self._antialiasing())
-            self._pending = [iteration + 1, vidx1, cam1, self.low_pass, next_frame, None]
-            self.low_pass = low_pass_now
+        if (fuse_adam and self.fuse_next and iteration + 1 < opt.iterations and not prune_now
+                and not (g.active_sh_degree < g.max_sh_degree and self._sh_ramp(iteration + 1))
+                and not (lam_n or lam_t or o.normal_weight(iteration + 1) or o.dist_weight(iteration + 1))):
+            vidx1, cam1, low_pass1 = self._low_pass_and_view(iteration + 1)
+            next_frame = fused.prepare_next(g, cam1, self.background, low_pass1, antialiasing=o.antialiasing)
+            self._pending = PendingFrame(iteration + 1, vidx1, cam1, low_pass1, next_frame)
         with torch.no_grad():
-            cache = self._bin_cache if self.reuse_binning else None
             if nxt is not None:
                 image, radii, _depth, st = fused.forward_next(nxt, g, cache=cache)
             else:
                 image, radii, _depth, st = fused.forward(g, cam, self.background, self.low_pass, cache=cache,
-                                                         normal=bool(lam_n),
-                                                         dist=self._dist_range() if lam_t else None,
-                                                         antialiasing=self._antialiasing())
+                                                         normal=bool(lam_n), dist=o.dist_range if lam_t else None,
+                                                         antialiasing=o.antialiasing)
             # loss and dL/dimage in one call (bitwise the separate forward / backward)
             loss, _parts, dimg = l1_ssim_forward_backward(image, gt, opt.lambda_dssim)
             if lam_n or lam_t:
@@ -564,19 +568,20 @@ class Trainer:
             else:
                 # (the absolute sums only feed the statistics: past the densify phase the plain backward runs)
                 fused.backward(st, dimg, grads, stats, adam=adam, next_frame=next_frame,
-                               absgrad=self._absgrad_on and stats is not None)
-            densified = self._finish(iteration, flat, densify_now, reset_now, adam_done=fuse_adam)
+                               absgrad=o.absgrad and stats is not None)
+            densified = self._densify_and_adam(iteration, adam_done=fuse_adam)
         if prune_now:  # after the optimizer step; no next-frame geometry was prepared
             self._importance_prune()
-        if self._pending is not None:  # the parameters the pending geometry was computed from
-            self._pending[5] = self._params_signature()
-        return StepInfo(loss=float(loss.item()) if sync_loss else None, num_gaussians=g.get_xyz.shape[0],
-                        view=vidx, low_pass=self.low_pass, densified=densified)
+        if self._pending is not None:
+            self._pending.signature = self._params_signature()
+        return self._info(loss, sync_loss, vidx, densified)
 
-    def _finish(self, iteration, flat, densify_now, reset_now, adam_done=False):
-        """Gradient exchange + optimizer step + densification (train.py:132-147) after the backward.
+    def _finish(self, iteration, flat, densify_now, reset_now):
+        """Gradient exchange + optimizer step + densification (train.py:132-147) after the backward of
+        the autograd step, the only one with a replicated exchange (the fused steps call
+        _densify_and_adam themselves).
 
-        N = 1: densify / reset, then Adam (unless the backward kernel already applied it).
+        N = 1: densify / reset, then Adam.
         N > 1, ordinary iteration (no densify / reset): reduce-scatter the flat gradient SUM, each
         rank runs Adam (scaled by 1/N) on its 1/N slice of the flat parameter / moment buffers, then
         all-gathers the parameter buffer — the bytes of one all-reduce, 1/N of the optimizer work.
@@ -586,7 +591,7 @@ class Trainer:
         steps every group but the replaced opacity), then the N = 1 logic on identical replicas."""
         g, opt = self.g, self.opt
         if not self.sharded:
-            return self._densify_and_adam(iteration, adam_done=adam_done)
+            return self._densify_and_adam(iteration)
         fp, fm, fv, _offs, n = g.pack_flat_state(self.world)
         S = n // self.world
         lo = self.rank * S
@@ -632,14 +637,12 @@ class Trainer:
 
     def _step_autograd(self, iteration: int, sync_loss: bool = False) -> StepInfo:
         """The reference-API step: render() through GaussianRasterizer + autograd (train.py:109-147)."""
-        g, opt = self.g, self.opt
-        lam_n = self._geometry_weight(iteration)
-        lam_t = self._distortion_weight(iteration)
-        prune_now = self._importance_prune_now(iteration)
-        vidx, cam = self._low_pass_and_view(iteration)
+        g, opt, o = self.g, self.opt, self.options
+        lam_n, lam_t = o.normal_weight(iteration), o.dist_weight(iteration)
+        vidx, cam, self.low_pass = self._low_pass_and_view(iteration)
         densify_phase = iteration < opt.densify_until_iter
         densify_now, reset_now = self._events(iteration)
-        absgrad = self._absgrad_on and densify_phase  # the absolute sums only feed the statistics
+        absgrad = o.absgrad and densify_phase  # the absolute sums only feed the statistics
         if self.sharded:  # gradients accumulate into the flat buffer the exchange reduces
             g.pack_flat_state(self.world)
             flat = g.bind_flat_grad(pad_to=self.world)
@@ -649,7 +652,7 @@ class Trainer:
                 p.grad = None
 
         if lam_t:
-            near, far = self._dist_range()
+            near, far = o.dist_range
             pkg = render(cam, g, self.pipe, self.background, low_pass=self.low_pass, normal_grad=bool(lam_n),
                          dist_grad=True, dist_near=near, dist_far=far)
         else:
@@ -672,10 +675,9 @@ class Trainer:
                 g.update_max_radii(radii, vis)
                 g.add_densification_stats(vsp, vis, absgrad=absgrad)
             densified = self._finish(iteration, flat, densify_now, reset_now)
-        if prune_now:
+        if o.prune_at(iteration):
             self._importance_prune()
-        return StepInfo(loss=float(loss.item()) if sync_loss else None, num_gaussians=g.get_xyz.shape[0],
-                        view=vidx, low_pass=self.low_pass, densified=densified)
+        return self._info(loss, sync_loss, vidx, densified)
 
     def _step_mcmc(self, iteration: int, sync_loss: bool = False) -> StepInfo:
         """The step under densify_strategy "mcmc" (rain_amd/mcmc.py), single GPU or CPU: the schedule of
@@ -687,24 +689,17 @@ class Trainer:
         update is skipped (step counts stay) and only the noise is applied.  No opacity reset ever runs."""
         from . import mcmc
 
-        g, opt, cfg = self.g, self.opt, self.cfg
-        vidx, cam = self._low_pass_and_view(iteration)
-        event = (cfg.densify and opt.densify_from_iter < iteration < opt.densify_until_iter
-                 and iteration % opt.densification_interval == 0)
+        g, opt = self.g, self.opt
+        vidx, cam, self.low_pass = self._low_pass_and_view(iteration)
+        event, _reset = self._events(iteration)
         gt = self.gt[vidx]
         if self.fused:
             from . import fused
-            from .loss import l1_ssim_forward_backward
 
-            if self._bin_cache is None:
-                self._bin_cache = fused.BinningCache()
-            g.bind_flat_grad(zero=False)  # the backward overwrites every gradient
-            grads = dict(xyz=g._xyz.grad, f_dc=g._features_dc.grad, f_rest=g._features_rest.grad,
-                         opacity=g._opacity.grad, scaling=g._scaling.grad, rotation=g._rotation.grad)
+            cache, grads = self._binning(), self._bind_grads()
             with torch.no_grad():
-                image, _radii, _depth, st = fused.forward(g, cam, self.background, self.low_pass,
-                                                          cache=self._bin_cache if self.reuse_binning else None,
-                                                          antialiasing=self._antialiasing())
+                image, _radii, _depth, st = fused.forward(g, cam, self.background, self.low_pass, cache=cache,
+                                                          antialiasing=self.options.antialiasing)
                 loss, _parts, dimg = l1_ssim_forward_backward(image, gt, opt.lambda_dssim)
                 fused.backward(st, dimg, grads, None)
         else:
@@ -721,5 +716,4 @@ class Trainer:
                 noise = torch.randn((g.get_xyz.shape[0], 3), device=g.get_xyz.device, generator=self.noise_gen)
                 mcmc.step(g, noise, opt.noise_lr, opt.opacity_reg, opt.scale_reg, do_adam=not event)
             g.optimizer.zero_grad(set_to_none=True)
-        return StepInfo(loss=float(loss.item()) if sync_loss else None, num_gaussians=g.get_xyz.shape[0],
-                        view=vidx, low_pass=self.low_pass, densified=bool(event))
+        return self._info(loss, sync_loss, vidx, event)

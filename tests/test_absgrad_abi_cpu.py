@@ -150,24 +150,25 @@ def test_stand_in_c_without_the_switch(monkeypatch):
 
 
 def test_trainer_refusals():
-    from rain_amd.train import Trainer
+    from rain_amd.renderer import PipelineParams
+    from rain_amd.train import Trainer, resolve_options
 
     t = Trainer.__new__(Trainer)
-    t.opt, t.sharded = OptimizationParams(densify_absgrad=True), True
+    t.opt, t.pipe, t.sharded = OptimizationParams(densify_absgrad=True), PipelineParams(), True
     with pytest.raises(ValueError, match="densify_absgrad needs the single-GPU step"):
-        t._absgrad()
+        resolve_options(t.opt, t.pipe, t.sharded)
     t.sharded = False
-    assert t._absgrad() is True
+    assert resolve_options(t.opt, t.pipe, t.sharded).absgrad is True
     t.opt = OptimizationParams(densify_absgrad=True, densify_strategy="mcmc", cap_max=100)
     with pytest.raises(ValueError, match="densify_absgrad does not combine with densify_strategy 'mcmc'"):
-        t._absgrad()
+        resolve_options(t.opt, t.pipe, t.sharded)
     for k in ("lambda_normal", "lambda_dist"):
         t.opt = OptimizationParams(densify_absgrad=True, **{k: 0.05})
         with pytest.raises(ValueError, match="densify_absgrad does not combine with lambda_normal / lambda_dist"):
-            t._absgrad()
+            resolve_options(t.opt, t.pipe, t.sharded)
     t.opt, t.sharded = OptimizationParams(), True
-    assert t._absgrad() is False
-    assert "self._absgrad()" in inspect.getsource(Trainer.__init__)
+    assert resolve_options(t.opt, t.pipe, t.sharded).absgrad is False
+    assert "resolve_options(self.opt, self.pipe, self.sharded)" in inspect.getsource(Trainer.__init__)
 
 
 def test_c_refusals_without_gpu():

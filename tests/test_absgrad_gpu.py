@@ -419,7 +419,7 @@ def test_trainer_accumulates_absolute_statistics_and_densifies_on_them(gpu, binn
         g.training_setup(opt)
         t = Trainer(g, cams, gts, opt, PipelineParams(), cfg=TrainConfig(c2f=False, seed=3), scene_extent=4.4,
                     fused=fuse)
-        assert t._absgrad() is on
+        assert t.options.absgrad is on
         for it in (1, 2, 3):
             assert not t.step(it).densified
             if it == 1:  # formed on the initial parameters, which the three runs share bit for bit

@@ -102,17 +102,18 @@ def test_python_refusals_without_gpu():
 
 
 def test_sharded_trainers_refuse_at_construction():
-    from rain_amd.train import Trainer
+    from rain_amd.gaussian_model import OptimizationParams
+    from rain_amd.train import Trainer, resolve_options
 
     t = Trainer.__new__(Trainer)
-    t.pipe, t.sharded = PipelineParams(antialiasing=True), True
+    t.opt, t.pipe, t.sharded = OptimizationParams(), PipelineParams(antialiasing=True), True
     with pytest.raises(ValueError, match="pipe.antialiasing needs the single-GPU step"):
-        t._antialiasing()
+        resolve_options(t.opt, t.pipe, t.sharded)
     t.sharded = False
-    assert t._antialiasing() is True
+    assert resolve_options(t.opt, t.pipe, t.sharded).antialiasing is True
     t.pipe = PipelineParams()
-    assert t._antialiasing() is False
-    assert "self._antialiasing()" in inspect.getsource(Trainer.__init__)
+    assert resolve_options(t.opt, t.pipe, t.sharded).antialiasing is False
+    assert "resolve_options(self.opt, self.pipe, self.sharded)" in inspect.getsource(Trainer.__init__)
 
 
 def test_c_refusals_without_gpu():

@@ -173,7 +173,7 @@ def _ref_loss(img, gt, lam):
 
 def test_sharded_trainer_refuses_importance_pruning():
     from rain_amd.renderer import PipelineParams
-    from rain_amd.train import TrainConfig, Trainer
+    from rain_amd.train import TrainConfig, Trainer, resolve_options
 
     def trainer(**kw):
         g = GaussianModel(1, divide_ratio=0.8, device="cpu")
@@ -187,13 +187,14 @@ def test_sharded_trainer_refuses_importance_pruning():
 
     t = trainer(importance_prune_iterations=(6,), importance_prune_fraction=0.3)
     assert not t.sharded
-    assert not t._importance_prune_now(5) and t._importance_prune_now(6)
+    assert not t.options.prune_at(5) and t.options.prune_at(6)
     t.sharded = True  # what world > 1 (or a forced exchange) sets; no ranks are started
     for it in (1, 6):
         with pytest.raises(ValueError, match="importance_prune_iterations needs the single-GPU step"):
             t.step(it)
     t0 = trainer()  # the defaults pass, sharded or not, and never prune
     t0.sharded = True
-    assert not any(t0._importance_prune_now(it) for it in (0, 1, 6, 30_000))
+    o0 = resolve_options(t0.opt, t0.pipe, t0.sharded)
+    assert not any(o0.prune_at(it) for it in (0, 1, 6, 30_000))
     t1 = trainer(importance_prune_iterations=(6,))  # no fraction: nothing to remove
-    assert not t1._importance_prune_now(6)
+    assert not t1.options.prune_at(6)

@@ -285,7 +285,7 @@ def test_sharded_trainer_refuses_lambda_dist():
     """The sharded / multi-rank steps have no depth-moment backward: a non-zero lambda_dist is a
     ValueError (at construction when the trainer is sharded from the start, else at the step)."""
     from rain_amd.renderer import PipelineParams
-    from rain_amd.train import TrainConfig, Trainer
+    from rain_amd.train import TrainConfig, Trainer, resolve_options
 
     def trainer(**kw):
         g = GaussianModel(1, divide_ratio=0.8, device="cpu")
@@ -305,9 +305,10 @@ def test_sharded_trainer_refuses_lambda_dist():
     with pytest.raises(ValueError, match="lambda_dist > 0 needs the single-GPU step"):
         t.step(5000)
     with pytest.raises(ValueError, match="lambda_dist > 0 needs the single-GPU step"):
-        t._distortion_weight(0)  # before lambda_dist_from_iter too: the configuration is refused
+        resolve_options(t.opt, t.pipe, t.sharded)  # whatever lambda_dist_from_iter: the configuration is refused
     t0 = trainer()  # the default weight passes
     t0.sharded = True
-    assert t0._distortion_weight(1) == 0.0 and t0._distortion_weight(10_000) == 0.0
+    o0 = resolve_options(t0.opt, t0.pipe, t0.sharded)
+    assert o0.dist_weight(1) == 0.0 and o0.dist_weight(10_000) == 0.0
     t1 = trainer(lambda_dist=0.1)
-    assert t1._distortion_weight(2999) == 0.0 and t1._distortion_weight(3000) == pytest.approx(0.1)
+    assert t1.options.dist_weight(2999) == 0.0 and t1.options.dist_weight(3000) == pytest.approx(0.1)

@@ -193,4 +193,4 @@ def test_trainer_refusals():
     with pytest.raises(ValueError, match="'mcmc' needs the single-GPU step"):
         t.step(1)
     t0 = _trainer()  # the default strategy: no MCMC state, cap_max unread
-    assert t0.noise_gen is None and not t0._mcmc()
+    assert t0.noise_gen is None and not t0.options.mcmc

@@ -135,6 +135,43 @@ def test_ours_new_warmup_abe_split_and_lr_shift(cpu_rasterizer):
     assert sizes["ours_new"] > sizes["plain"]  # the abe copies (N - 1 = 1 per kept split Gaussian)
 
 
+def test_resolve_options_defaults_and_refusal_order():
+    """Parameter objects without the newer fields mean every opt-in mode off; with several violations at
+    once the refusal is the first in the resolver's documented order; prune iterations need a fraction."""
+    from types import SimpleNamespace
+
+    from rain_amd.train import StepOptions, resolve_options
+
+    bare = resolve_options(SimpleNamespace(), SimpleNamespace(), True)
+    assert bare == StepOptions(mcmc=False, absgrad=False, antialiasing=False, lambda_normal=0.0,
+                               lambda_normal_from_iter=0, lambda_dist=0.0, lambda_dist_from_iter=0,
+                               dist_range=(0.2, 100.0), prune_iterations=())
+    assert bare == resolve_options(OptimizationParams(lambda_normal_from_iter=0, lambda_dist_from_iter=0),
+                                   PipelineParams(), True)
+    everything = OptimizationParams(lambda_normal=0.05, lambda_dist=0.1, importance_prune_iterations=(6,),
+                                    densify_absgrad=True, densify_strategy="adc")
+    aa = PipelineParams(antialiasing=True)
+    with pytest.raises(ValueError, match="lambda_normal > 0 needs the single-GPU step"):
+        resolve_options(everything, aa, True)
+    everything.lambda_normal = 0.0
+    with pytest.raises(ValueError, match="lambda_dist > 0 needs the single-GPU step"):
+        resolve_options(everything, aa, True)
+    everything.lambda_dist = -1.0  # no weight, but a set field for the modes that refuse the lambdas
+    with pytest.raises(ValueError, match="importance_prune_iterations needs the single-GPU step"):
+        resolve_options(everything, aa, True)
+    with pytest.raises(ValueError, match="densify_absgrad does not combine with lambda_normal / lambda_dist"):
+        resolve_options(everything, aa, False)
+    everything.densify_absgrad = False
+    with pytest.raises(ValueError, match="must be 'default' or 'mcmc', got 'adc'"):
+        resolve_options(everything, aa, False)
+    everything.densify_strategy = "default"
+    o = resolve_options(everything, aa, False)
+    assert o.antialiasing and o.lambda_dist == 0.0 and o.prune_iterations == () and not o.prune_at(6)
+    everything.importance_prune_fraction = 0.3
+    o = resolve_options(everything, aa, False)
+    assert o.prune_iterations == (6,) and o.prune_at(6) and not o.prune_at(5)
+
+
 # ---- view-sharded data parallel over gloo ------------------------------------------------
 
 def _scene():
